@@ -7,11 +7,17 @@ python bench.py --gpus N --steps K --warmup W
     nx by sqrt(N), the reference protocol)
   - rank 0 prints ONE JSON line; value = whole-job CG iterations/sec.
 
-Besides the headline it measures (a) standalone CSR SpMV GFLOP/s and
+A plain run does only what the headline needs: set up, warm up, time the
+K steps, print the line.  --dump-outputs DIR additionally writes what the
+last timed step left behind (x, r, p, q, rz) as DIR/<name>.npy so two
+builds can be compared output for output (inputs are deterministic).
+
+With --full it also measures (a) standalone CSR SpMV GFLOP/s and
 (b) the MATCHED reference config — nx=6000 per GPU, sqrt(N)-weak-scaled,
 the exact grid the reference's 75.9 it/s V100 number is quoted on
 (results/summit/legate_gpu_pde.out) — so both the headline-vs-baseline
-and the apples-to-apples ratios are machine-readable (config.matched_*).
+and the apples-to-apples ratios are machine-readable (config.spmv_*,
+config.matched_*).
 """
 from __future__ import annotations
 
@@ -170,6 +176,42 @@ def time_steps(cg_step, steps, warmup, sync):
     return float(et.item())
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept per vector when it is sampled
+DUMP_WHOLE_BYTES = 8 << 20  # vectors up to this size are written whole
+DUMP_SEED = 20240229
+
+
+def dump_outputs(dirname, state, rank, ws) -> None:
+    """Write the CG state after the last timed step as DIR/<name>.npy
+    (fp32/fp64, < 64 MB in all).  Vectors larger than DUMP_WHOLE_BYTES are
+    reduced to a fixed seeded sample of DUMP_SAMPLE elements; the sampled
+    positions go to sample_index.npy.  At ws>1 every rank writes its own
+    slab as <name>_rank<r>.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if ws > 1 else ""
+
+    def save(name, arr) -> None:
+        arr = np.ascontiguousarray(arr)
+        if arr.dtype not in (np.float32, np.float64):
+            arr = arr.astype(np.float64)
+        np.save(os.path.join(dirname, f"{name}{sfx}.npy"), arr)
+
+    # p_b: second p buffer of the double-buffered SPARSE_CG2 loop
+    vecs = {k: state[k].local for k in ("x", "r", "p", "q", "p_b")
+            if k in state}
+    m = vecs["x"].numel()
+    idx = None
+    if m * vecs["x"].element_size() > DUMP_WHOLE_BYTES:
+        rng = np.random.default_rng(DUMP_SEED + rank)
+        pos = np.sort(rng.choice(m, size=DUMP_SAMPLE, replace=False))
+        save("sample_index", pos.astype(np.float64))  # exact below 2^53
+        idx = torch.from_numpy(pos).to(vecs["x"].device)
+    for name, t in vecs.items():
+        save(name, (t if idx is None else t[idx]).cpu().numpy())
+    save("rz", state.get("rz_buf", state["rz"]).detach().cpu().numpy()
+         .reshape(1))
+
+
 def main() -> None:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -179,8 +221,14 @@ def main() -> None:
     p.add_argument("--dtype", default="fp64", choices=["fp64", "fp32"])
     p.add_argument("--weak", action="store_true",
                    help="scale nx by sqrt(world) (reference weak-scaling protocol)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure standalone SpMV and the matched "
+                        "reference config (nx=6000/GPU)")
     p.add_argument("--no-matched", action="store_true",
-                   help="skip the matched-config (nx=6000/GPU) measurement")
+                   help="with --full: skip the matched-config measurement")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the CG state after the last timed step as "
+                        "DIR/<name>.npy")
     args = p.parse_args()
 
     import sparse  # noqa: F401
@@ -213,25 +261,30 @@ def main() -> None:
         if on_gpu:
             torch.cuda.synchronize()
 
-    # -- standalone SpMV measurement (secondary metric) ----------------------
-    x = darray.ones((n,), dtype=dtype)
-    y = darray.zeros((n,), dtype=dtype)
-    for _ in range(3):
-        A.dot(x, out=y)
-    sync()
-    t0 = time.time()
-    SPMV_IT = 10
-    for _ in range(SPMV_IT):
-        A.dot(x, out=y)
-    sync()
-    spmv_s = (time.time() - t0) / SPMV_IT
     nnz = A.nnz
-    spmv_gflops = 2.0 * nnz / spmv_s / 1e9
-    # bytes: vals + idx + indptr + x-read + y-write (first-order)
-    idx_b = 4 if max(A.shape) < 2**31 - 1 else 8
-    vb = np.dtype(dtype).itemsize
-    spmv_gbps = (nnz * (vb + idx_b) + n * (3 * vb)) / spmv_s / 1e9
-    del x, y
+    extra = {}
+
+    # -- standalone SpMV measurement (secondary metric, --full) --------------
+    if args.full:
+        x = darray.ones((n,), dtype=dtype)
+        y = darray.zeros((n,), dtype=dtype)
+        for _ in range(3):
+            A.dot(x, out=y)
+        sync()
+        t0 = time.time()
+        SPMV_IT = 10
+        for _ in range(SPMV_IT):
+            A.dot(x, out=y)
+        sync()
+        spmv_s = (time.time() - t0) / SPMV_IT
+        spmv_gflops = 2.0 * nnz / spmv_s / 1e9
+        # bytes: vals + idx + indptr + x-read + y-write (first-order)
+        idx_b = 4 if max(A.shape) < 2**31 - 1 else 8
+        vb = np.dtype(dtype).itemsize
+        spmv_gbps = (nnz * (vb + idx_b) + n * (3 * vb)) / spmv_s / 1e9
+        del x, y
+        extra["spmv_gflops"] = round(spmv_gflops, 2)
+        extra["spmv_effective_gbps"] = round(spmv_gbps, 1)
 
     # -- headline CG loop ----------------------------------------------------
     # ws>1 capture (RCCL collectives inside the hipGraph) is opt-in until
@@ -243,11 +296,13 @@ def main() -> None:
     elapsed = time_steps(cg_step, args.steps, args.warmup, sync)
     iters_per_sec = args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, _state, comm.rank(), ws)
 
-    # -- matched reference config: nx=6000 per GPU, sqrt(N)-weak ------------
+    # -- matched reference config: nx=6000 per GPU, sqrt(N)-weak (--full) ---
     matched = None
     m_nx = int(round(MATCHED_NX * math.sqrt(ws)))
-    if on_gpu and not args.no_matched and m_nx != nx:
+    if args.full and on_gpu and not args.no_matched and m_nx != nx:
         del cg_step, _state, A, b
         torch.cuda.empty_cache()
         m_n = m_nx * m_nx
@@ -284,8 +339,7 @@ def main() -> None:
                 "n": n,
                 "nnz": nnz,
                 "parallelism": f"dp{args.gpus} 1-D row partition + window gather",
-                "spmv_gflops": round(spmv_gflops, 2),
-                "spmv_effective_gbps": round(spmv_gbps, 1),
+                **extra,
                 "build_s": round(build_s, 2),
                 **(matched or {}),
             },

@@ -7,7 +7,7 @@ ITERS=300; STEPS=60
 if [ "$QUICK" = "quick" ]; then ITERS=50; STEPS=20; fi
 
 # headline: CG on 5-pt Poisson (BASELINE.json config)
-python bench.py --steps $STEPS --warmup 10 --nx 16384
+python bench.py --full --steps $STEPS --warmup 10 --nx 16384
 
 # reference's own headline config (75.9 it/s on V100)
 python examples/pde.py -nx 6000 -ny 6000 -throughput -max_iter $ITERS
@@ -36,10 +36,10 @@ hipcc --offload-arch=gfx950 -O3 tools/mfma_spmm_bench.hip -o /tmp/mfma_bench
 /tmp/mfma_bench --probe && /tmp/mfma_bench 1048576 30
 
 # capacity: 604M rows / 3.02B nnz on ONE GPU (288 GB sizing)
-python bench.py --nx 24576 --steps 30 --warmup 5
+python bench.py --full --nx 24576 --steps 30 --warmup 5
 
 # fp32 option
-python bench.py --nx 8192 --dtype fp32 --steps $STEPS --warmup 10
+python bench.py --full --nx 8192 --dtype fp32 --steps $STEPS --warmup 10
 
 # 8-GPU strong scaling (run on an 8-GPU node; the driver does this too)
 # python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \

@@ -9,6 +9,12 @@ import sys
 
 import pytest
 
+# These are the gloo/CPU runs: where a GPU is present the ranks would
+# otherwise pick RCCL and collide on the one device (the ranks-share-a-GPU
+# variants live in test_multigpu.py).
+_CPU_GLOO = {"SPARSE_DIST_BACKEND": "gloo", "CUDA_VISIBLE_DEVICES": "",
+             "HIP_VISIBLE_DEVICES": ""}
+
 
 @pytest.mark.parametrize("nproc", [2, 3, 4])
 def test_distributed_battery(nproc):
@@ -56,7 +62,7 @@ def test_bench_multirank(nproc, extra):
     env.update({"MASTER_ADDR": "127.0.0.1",
                 "MASTER_PORT": str(29810 + nproc + len(extra)),
                 "GLOO_SOCKET_IFNAME": env.get("GLOO_SOCKET_IFNAME", "lo"),
-                "WORLD_SIZE": str(nproc)})
+                "WORLD_SIZE": str(nproc), **_CPU_GLOO})
     nx = "128" if nproc == 2 else "64"
     argv = [sys.executable, os.path.join(root, "bench.py"),
             "--gpus", str(nproc), "--steps", "4", "--warmup", "1",
@@ -105,7 +111,7 @@ def test_examples_multirank():
         env = dict(os.environ)
         env.update({"MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(29930 + i),
                     "GLOO_SOCKET_IFNAME": env.get("GLOO_SOCKET_IFNAME", "lo"),
-                    "WORLD_SIZE": "2"})
+                    "WORLD_SIZE": "2", **_CPU_GLOO})
         procs = []
         for r in range(2):
             e = dict(env)
