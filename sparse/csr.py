@@ -311,7 +311,8 @@ class csr_array(CompressedBase, DenseSparseBase):
     def _ell_interior(self, ell, plan):
         """Even row bounds [a, b) of the longest contiguous interior run —
         rows whose whole column window lies in the own x piece (the ELL
-        analog of _dia_interior; (0, 0) disables the overlap split)."""
+        analog of _dia_interior), or None when the interior is too small
+        to be worth the overlap split."""
         me = comm.rank()
         key = ("ell_int", plan.lo, plan.hi, plan.xpart.starts)
         if key not in self._plan_cache:
@@ -321,7 +322,30 @@ class csr_array(CompressedBase, DenseSparseBase):
             own_a = max(plan.lo, xs)
             own_b = max(own_a, min(plan.hi, xe))
             self._plan_cache[key] = kernels.ell_interior(ell, own_a, own_b)
-        return self._plan_cache[key]
+        a, b = self._plan_cache[key]
+        return (a, b) if b > a else None
+
+    def _halo_split(self, plan, xlocal, interior, launch):
+        """Run launch(pieces, rbase, rhi) over all local rows, overlapping
+        the halo exchange of xlocal with the interior rows at ws>1.
+
+        interior() gives the even row bounds (a, b) of the rows that read
+        only the own x piece, or None for no split; it is evaluated only
+        when the overlap applies.  Those rows run on handle_pieces while
+        the exchange is in flight, then [0, a) and [b, end) run on the
+        complete pieces.  launch returns None or a 0-dim partial dot; the
+        partial dots are summed."""
+        split = None
+        if comm.world_size() > 1 and not os.environ.get("SPARSE_NO_OVERLAP"):
+            split = interior()
+        if split is None:
+            return launch(plan.gather_halos(xlocal), 0, -1)
+        a, b = split
+        h = plan.gather_halos_begin(xlocal)
+        mid = launch(plan.handle_pieces(h), a, b)
+        pieces = plan.gather_halos_end(h)
+        lo, hi = launch(pieces, 0, a), launch(pieces, b, -1)
+        return None if mid is None else mid + lo + hi
 
     def _dia(self):
         """Cached diagonal mirror (GPU banded fast SpMV; kernels.build_dia —
@@ -582,35 +606,18 @@ class csr_array(CompressedBase, DenseSparseBase):
             from . import kernels
 
             ylocal = _ybuf()
-            ws_ = plan.hi - plan.lo
-            if comm.world_size() > 1 and not os.environ.get("SPARSE_NO_OVERLAP"):
-                h = plan.gather_halos_begin(x.local.to(vdt))
-                a, bnd = self._dia_interior(dm, plan)
-                kernels.dia_spmv(dm, plan.handle_pieces(h), ylocal, plan.lo,
-                                 ws_, a, bnd)
-                pieces = plan.gather_halos_end(h)
-                kernels.dia_spmv(dm, pieces, ylocal, plan.lo, ws_, 0, a)
-                kernels.dia_spmv(dm, pieces, ylocal, plan.lo, ws_, bnd, -1)
-            else:
-                pieces = plan.gather_halos(x.local.to(vdt))
-                kernels.dia_spmv(dm, pieces, ylocal, plan.lo, ws_)
+            self._halo_split(
+                plan, x.local.to(vdt), lambda: self._dia_interior(dm, plan),
+                lambda pieces, rbase, rhi: kernels.dia_spmv(
+                    dm, pieces, ylocal, plan.lo, plan.hi - plan.lo, rbase, rhi))
         elif ell is not None:
             from . import kernels
 
             ylocal = _ybuf()
-            a = b = 0
-            if comm.world_size() > 1 and not os.environ.get("SPARSE_NO_OVERLAP"):
-                a, b = self._ell_interior(ell, plan)
-            if b > a:
-                h = plan.gather_halos_begin(x.local.to(vdt))
-                kernels.ell_spmv(ell, plan.handle_pieces(h), ylocal,
-                                 plan.lo, a, b)
-                pieces = plan.gather_halos_end(h)
-                kernels.ell_spmv(ell, pieces, ylocal, plan.lo, 0, a)
-                kernels.ell_spmv(ell, pieces, ylocal, plan.lo, b, -1)
-            else:
-                pieces = plan.gather_halos(x.local.to(vdt))
-                kernels.ell_spmv(ell, pieces, ylocal, plan.lo)
+            self._halo_split(
+                plan, x.local.to(vdt), lambda: self._ell_interior(ell, plan),
+                lambda pieces, rbase, rhi: kernels.ell_spmv(
+                    ell, pieces, ylocal, plan.lo, rbase, rhi))
         else:
             xw = plan.gather(x.local.to(vdt))
             self._max_row_nnz()
@@ -721,22 +728,11 @@ class csr_array(CompressedBase, DenseSparseBase):
             from . import kernels
 
             plan = self._xplan(x.partition)
-            ws_ = plan.hi - plan.lo
-            if comm.world_size() > 1 and not os.environ.get("SPARSE_NO_OVERLAP"):
-                h = plan.gather_halos_begin(x.local)
-                a, bnd = self._dia_interior(dm, plan)
-                kernels.dia_jacobi(dm, plan.handle_pieces(h), x.local,
-                                   b.local, dinv.local, omega, out.local,
-                                   plan.lo, ws_, a, bnd)
-                pieces = plan.gather_halos_end(h)
-                kernels.dia_jacobi(dm, pieces, x.local, b.local, dinv.local,
-                                   omega, out.local, plan.lo, ws_, 0, a)
-                kernels.dia_jacobi(dm, pieces, x.local, b.local, dinv.local,
-                                   omega, out.local, plan.lo, ws_, bnd, -1)
-            else:
-                pieces = plan.gather_halos(x.local)
-                kernels.dia_jacobi(dm, pieces, x.local, b.local, dinv.local,
-                                   omega, out.local, plan.lo, ws_)
+            self._halo_split(
+                plan, x.local, lambda: self._dia_interior(dm, plan),
+                lambda pieces, rbase, rhi: kernels.dia_jacobi(
+                    dm, pieces, x.local, b.local, dinv.local, omega,
+                    out.local, plan.lo, plan.hi - plan.lo, rbase, rhi))
             return out
         if ell is not None:
             from . import kernels
@@ -771,21 +767,11 @@ class csr_array(CompressedBase, DenseSparseBase):
             from . import kernels
 
             plan = self._xplan(x.partition)
-            ws_ = plan.hi - plan.lo
-            if comm.world_size() > 1 and not os.environ.get("SPARSE_NO_OVERLAP"):
-                h = plan.gather_halos_begin(x.local)
-                a, bnd = self._dia_interior(dm, plan)
-                kernels.dia_residual(dm, plan.handle_pieces(h), b.local,
-                                     out.local, plan.lo, ws_, a, bnd)
-                pieces = plan.gather_halos_end(h)
-                kernels.dia_residual(dm, pieces, b.local, out.local,
-                                     plan.lo, ws_, 0, a)
-                kernels.dia_residual(dm, pieces, b.local, out.local,
-                                     plan.lo, ws_, bnd, -1)
-            else:
-                pieces = plan.gather_halos(x.local)
-                kernels.dia_residual(dm, pieces, b.local, out.local,
-                                     plan.lo, ws_)
+            self._halo_split(
+                plan, x.local, lambda: self._dia_interior(dm, plan),
+                lambda pieces, rbase, rhi: kernels.dia_residual(
+                    dm, pieces, b.local, out.local, plan.lo,
+                    plan.hi - plan.lo, rbase, rhi))
             return out
         self._spmv(x, out=out)
         out.local.sub_(b.local).neg_()
@@ -809,38 +795,16 @@ class csr_array(CompressedBase, DenseSparseBase):
         ell = None if dm is not None else (
             self._ell() if not precise else None)
         if dm is not None:
-            ws_ = plan.hi - plan.lo
-            if comm.world_size() > 1 and not os.environ.get("SPARSE_NO_OVERLAP"):
-                h = plan.gather_halos_begin(p.local)
-                a, bnd = self._dia_interior(dm, plan)
-                dot = kernels.dia_spmv_dot(dm, plan.handle_pieces(h), q.local,
-                                           p.local, plan.lo, ws_, a, bnd)
-                pieces = plan.gather_halos_end(h)
-                dot = dot + kernels.dia_spmv_dot(dm, pieces, q.local, p.local,
-                                                 plan.lo, ws_, 0, a)
-                dot = dot + kernels.dia_spmv_dot(dm, pieces, q.local, p.local,
-                                                 plan.lo, ws_, bnd, -1)
-            else:
-                pieces = plan.gather_halos(p.local)
-                dot = kernels.dia_spmv_dot(dm, pieces, q.local, p.local,
-                                           plan.lo, ws_)
+            dot = self._halo_split(
+                plan, p.local, lambda: self._dia_interior(dm, plan),
+                lambda pieces, rbase, rhi: kernels.dia_spmv_dot(
+                    dm, pieces, q.local, p.local, plan.lo, plan.hi - plan.lo,
+                    rbase, rhi))
         elif ell is not None:
-            a = b = 0
-            if comm.world_size() > 1 and not os.environ.get("SPARSE_NO_OVERLAP"):
-                a, b = self._ell_interior(ell, plan)
-            if b > a:
-                h = plan.gather_halos_begin(p.local)
-                dot = kernels.ell_spmv_dot(ell, plan.handle_pieces(h),
-                                           q.local, p.local, plan.lo, a, b)
-                pieces = plan.gather_halos_end(h)
-                dot = dot + kernels.ell_spmv_dot(ell, pieces, q.local,
-                                                 p.local, plan.lo, 0, a)
-                dot = dot + kernels.ell_spmv_dot(ell, pieces, q.local,
-                                                 p.local, plan.lo, b, -1)
-            else:
-                pieces = plan.gather_halos(p.local)
-                dot = kernels.ell_spmv_dot(ell, pieces, q.local, p.local,
-                                           plan.lo)
+            dot = self._halo_split(
+                plan, p.local, lambda: self._ell_interior(ell, plan),
+                lambda pieces, rbase, rhi: kernels.ell_spmv_dot(
+                    ell, pieces, q.local, p.local, plan.lo, rbase, rhi))
         else:
             xw = plan.gather(p.local)
             dot = torch.zeros((), dtype=self._values.dtype, device=self._values.device)

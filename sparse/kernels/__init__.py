@@ -43,10 +43,10 @@ def require():
 
 # -- high-level wrappers ------------------------------------------------------
 def spmv(A, x, y, col_lo: int, beta: float):
-    # NOTE: a thread-per-row variant (csr_row_spmv) was measured 2.8x SLOWER
-    # than the nnz-split kernel on scattered-column short rows (its win in
+    # nnz-split is the general fallback: a thread-per-row loop measured 2.8x
+    # SLOWER on scattered-column short rows, and its win in
     # tools/spmv_bench.hip was banded-specific, where the ELL path applies
-    # anyway) — nnz-split stays the general fallback.
+    # anyway.
     ext().spmv(A.indptr, A.indices, A.values, x, y, int(col_lo), float(beta))
 
 
@@ -445,30 +445,28 @@ def build_dia(A, row0: int):
                      off_min=int(offs[0].item()), off_max=int(offs[-1].item()))
 
 
+def _pieces(p):
+    """(hlo, own, hhi) window pieces as contiguous tensors."""
+    hlo, own, hhi = p
+    return hlo.contiguous(), own.contiguous(), hhi.contiguous()
+
+
 def dia_spmv(dm: DiaMirror, pieces, y, col_lo: int, wsize: int,
              rbase: int = 0, rhi: int = -1):
     """rbase/rhi select a row sub-range (rbase even; -1 = all rows): the
     interior/boundary split that overlaps halo exchange with interior
     compute at ws>1."""
-    hlo, own, hhi = pieces
-    ext().dia_spmv(dm.dvals, dm.offs, hlo.contiguous(), own.contiguous(),
-                   hhi.contiguous(), y, dm.W, dm.m, int(col_lo), dm.row0,
-                   int(wsize), int(rbase), int(rhi))
+    ext().dia_spmv(dm.dvals, dm.offs, *_pieces(pieces), y, dm.W, dm.m,
+                   int(col_lo), dm.row0, int(wsize), int(rbase), int(rhi))
 
 
 def dia_spmv_dot(dm: DiaMirror, pieces, y, p, col_lo: int, wsize: int,
                  rbase: int = 0, rhi: int = -1):
-    hlo, own, hhi = pieces
-    mp = dm.dvals.numel() // dm.W
-    hi = mp if rhi < 0 else rhi
-    nblocks = max(1, ((hi - rbase) // 2 + 256) // 256)
-    partial = torch.empty(nblocks, dtype=dm.dvals.dtype, device=dm.dvals.device)
-    if hi <= rbase:
-        return partial[:1].zero_().sum()
-    ext().dia_spmv_dot(dm.dvals, dm.offs, hlo.contiguous(), own.contiguous(),
-                       hhi.contiguous(), y, p, partial, dm.W, dm.m,
-                       int(col_lo), dm.row0, int(wsize), int(rbase), int(hi))
-    return partial.sum()
+    """Fused y = A@x ; returns sum(p * y) over the row range (device
+    0-dim, local partial-sum; exact zero for an empty range)."""
+    return ext().dia_spmv_dot(dm.dvals, dm.offs, *_pieces(pieces), y, p,
+                              dm.W, dm.m, int(col_lo), dm.row0, int(wsize),
+                              int(rbase), int(rhi))
 
 
 def dia_spmv_bpdot(dm: DiaMirror, r_pieces, p_pieces, pnew, q,
@@ -477,16 +475,10 @@ def dia_spmv_bpdot(dm: DiaMirror, r_pieces, p_pieces, pnew, q,
     returns p.q (device 0-dim, local partial-sum).  r_pieces/p_pieces are
     the (hlo, own, hhi) window pieces of r and p_old; pnew must be a
     distinct buffer from p_old (double-buffered caller)."""
-    rlo, rown, rhi = r_pieces
-    plo, pown, phi = p_pieces
-    mp = dm.dvals.numel() // dm.W
-    nblocks = (mp // 2 + 255) // 256
-    partial = torch.empty(nblocks, dtype=dm.dvals.dtype, device=dm.dvals.device)
-    ext().dia_spmv_bpdot(dm.dvals, dm.offs, rlo.contiguous(), rown.contiguous(),
-                         rhi.contiguous(), plo.contiguous(), pown.contiguous(),
-                         phi.contiguous(), pnew, q, beta_num, beta_den,
-                         partial, dm.W, dm.m, int(col_lo), dm.row0, int(wsize))
-    return partial.sum()
+    return ext().dia_spmv_bpdot(dm.dvals, dm.offs, *_pieces(r_pieces),
+                                *_pieces(p_pieces), pnew, q, beta_num,
+                                beta_den, dm.W, dm.m, int(col_lo), dm.row0,
+                                int(wsize))
 
 
 def cg_xr_norm2(x, p, r, q, a, b):
@@ -505,19 +497,15 @@ def cg_xr_norm2(x, p, r, q, a, b):
 def dia_residual(dm: DiaMirror, pieces, b, y, col_lo: int, wsize: int,
                  rbase: int = 0, rhi: int = -1):
     """Fused V-cycle residual y = b - A@x (x given as window pieces)."""
-    hlo, own, hhi = pieces
-    ext().dia_residual(dm.dvals, dm.offs, hlo.contiguous(), own.contiguous(),
-                       hhi.contiguous(), b, y, dm.W, dm.m, int(col_lo),
-                       dm.row0, int(wsize), int(rbase), int(rhi))
+    ext().dia_residual(dm.dvals, dm.offs, *_pieces(pieces), b, y, dm.W, dm.m,
+                       int(col_lo), dm.row0, int(wsize), int(rbase), int(rhi))
 
 
 def dia_jacobi(dm: DiaMirror, pieces, xloc, b, dinv, omega, xout,
                col_lo: int, wsize: int, rbase: int = 0, rhi: int = -1):
-    hlo, own, hhi = pieces
-    ext().dia_jacobi(dm.dvals, dm.offs, hlo.contiguous(), own.contiguous(),
-                     hhi.contiguous(), xloc, b, dinv, xout, dm.W, dm.m,
-                     int(col_lo), dm.row0, int(wsize), float(omega),
-                     int(rbase), int(rhi))
+    ext().dia_jacobi(dm.dvals, dm.offs, *_pieces(pieces), xloc, b, dinv, xout,
+                     dm.W, dm.m, int(col_lo), dm.row0, int(wsize),
+                     float(omega), int(rbase), int(rhi))
 
 
 # -- BSR (MFMA) fast path -----------------------------------------------------
@@ -658,30 +646,19 @@ def ell_interior(ell: EllMirror, own_a: int, own_b: int):
 
 def ell_spmv(ell: EllMirror, pieces, y, col_lo: int,
              rbase: int = 0, rhi: int = -1):
-    hlo, own, hhi = pieces
-    ext().ell_spmv(ell.eidx, ell.evals, hlo.contiguous(), own.contiguous(),
-                   hhi.contiguous(), y, ell.W, ell.m, int(col_lo),
-                   int(rbase), int(rhi))
+    ext().ell_spmv(ell.eidx, ell.evals, *_pieces(pieces), y, ell.W, ell.m,
+                   int(col_lo), int(rbase), int(rhi))
 
 
 def ell_jacobi(ell: EllMirror, pieces, xloc, b, dinv, omega, xout, col_lo: int):
     """Fused weighted-Jacobi sweep: xout = x + omega*dinv*(b - A x)."""
-    hlo, own, hhi = pieces
-    ext().ell_jacobi(ell.eidx, ell.evals, hlo.contiguous(), own.contiguous(),
-                     hhi.contiguous(), xloc, b, dinv, xout, ell.W, ell.m,
-                     int(col_lo), float(omega))
+    ext().ell_jacobi(ell.eidx, ell.evals, *_pieces(pieces), xloc, b, dinv,
+                     xout, ell.W, ell.m, int(col_lo), float(omega))
 
 
 def ell_spmv_dot(ell: EllMirror, pieces, y, p, col_lo: int,
                  rbase: int = 0, rhi: int = -1):
-    hlo, own, hhi = pieces
-    mp = ell.evals.numel() // ell.W
-    hi = mp if rhi < 0 else rhi
-    if hi <= rbase:
-        return torch.zeros((), dtype=ell.evals.dtype, device=ell.evals.device)
-    nblocks = ((hi - rbase) // 2 + 255) // 256 + 1
-    partial = torch.zeros(nblocks, dtype=ell.evals.dtype, device=ell.evals.device)
-    ext().ell_spmv_dot(ell.eidx, ell.evals, hlo.contiguous(), own.contiguous(),
-                       hhi.contiguous(), y, p, partial, ell.W, ell.m,
-                       int(col_lo), int(rbase), int(hi))
-    return partial.sum()
+    """Fused y = A@x ; returns sum(p * y) over the row range (device
+    0-dim, local partial-sum; exact zero for an empty range)."""
+    return ext().ell_spmv_dot(ell.eidx, ell.evals, *_pieces(pieces), y, p,
+                              ell.W, ell.m, int(col_lo), int(rbase), int(rhi))

@@ -11,8 +11,6 @@ void spmv_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
               int64_t, double);
 void spmv_dot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                   at::Tensor, at::Tensor, int64_t);
-void csr_row_spmv_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      at::Tensor, int64_t);
 void axpby_norm2_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, bool,
                      bool, at::Tensor);
 void build_ell_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
@@ -22,26 +20,25 @@ void build_dia_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
 void ell_spmv_plain_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                         at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
                         int64_t, int64_t);
-void ell_spmv_dot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      int64_t, int64_t, int64_t, int64_t, int64_t);
+at::Tensor ell_spmv_dot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                            at::Tensor, at::Tensor, at::Tensor, int64_t,
+                            int64_t, int64_t, int64_t, int64_t);
 void ell_jacobi_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, int64_t, int64_t, int64_t, double);
 void cg_xr_norm2_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                      at::Tensor, at::Tensor, at::Tensor);
-void dia_spmv_bpdot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                        at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                        at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                        at::Tensor, int64_t, int64_t, int64_t, int64_t,
-                        int64_t);
+at::Tensor dia_spmv_bpdot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                              at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                              at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                              int64_t, int64_t, int64_t, int64_t, int64_t);
 void dia_spmv_plain_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                         at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
                         int64_t, int64_t, int64_t, int64_t);
-void dia_spmv_dot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
-                      int64_t);
+at::Tensor dia_spmv_dot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                            at::Tensor, at::Tensor, at::Tensor, int64_t,
+                            int64_t, int64_t, int64_t, int64_t, int64_t,
+                            int64_t);
 void dia_residual_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
                       int64_t, int64_t, int64_t, int64_t, int64_t);
@@ -102,8 +99,6 @@ TORCH_LIBRARY(sparse_hip, m) {
         "bool negate) -> ()");
   m.def("spmv_dot(Tensor indptr, Tensor indices, Tensor values, Tensor x, "
         "Tensor(a!) y, Tensor pvec, Tensor(b!) dot_out, int col_lo) -> ()");
-  m.def("csr_row_spmv(Tensor indptr, Tensor indices, Tensor values, Tensor x, "
-        "Tensor(a!) y, int col_lo) -> ()");
   m.def("axpby_norm2(Tensor(a!) y, Tensor x, Tensor a, Tensor b, bool isalpha, "
         "bool negate, Tensor(b!) dot_out) -> ()");
   m.def("build_ell(Tensor indptr, Tensor indices, Tensor values, "
@@ -114,8 +109,8 @@ TORCH_LIBRARY(sparse_hip, m) {
         "Tensor hhi, Tensor(a!) y, int W, int m, int col_lo, "
         "int rbase, int rhi) -> ()");
   m.def("ell_spmv_dot(Tensor eidx, Tensor evals, Tensor hlo, Tensor own, "
-        "Tensor hhi, Tensor(a!) y, Tensor pvec, Tensor(b!) dot_partial, "
-        "int W, int m, int col_lo, int rbase, int rhi) -> ()");
+        "Tensor hhi, Tensor(a!) y, Tensor pvec, int W, int m, int col_lo, "
+        "int rbase, int rhi) -> Tensor");
   m.def("ell_jacobi(Tensor eidx, Tensor evals, Tensor hlo, Tensor own, "
         "Tensor hhi, Tensor xloc, Tensor b, Tensor dinv, Tensor(a!) xout, "
         "int W, int m, int col_lo, float omega) -> ()");
@@ -124,15 +119,13 @@ TORCH_LIBRARY(sparse_hip, m) {
   m.def("dia_spmv_bpdot(Tensor dvals, Tensor offs, Tensor r_hlo, Tensor r_own, "
         "Tensor r_hhi, Tensor p_hlo, Tensor p_own, Tensor p_hhi, "
         "Tensor(a!) pnew, Tensor(b!) q, Tensor beta_num, Tensor beta_den, "
-        "Tensor(c!) dot_partial, int W, int m, int col_lo, int row0, "
-        "int wsize) -> ()");
+        "int W, int m, int col_lo, int row0, int wsize) -> Tensor");
   m.def("dia_spmv(Tensor dvals, Tensor offs, Tensor hlo, Tensor own, "
         "Tensor hhi, Tensor(a!) y, int W, int m, int col_lo, int row0, "
         "int wsize, int rbase, int rhi) -> ()");
   m.def("dia_spmv_dot(Tensor dvals, Tensor offs, Tensor hlo, Tensor own, "
-        "Tensor hhi, Tensor(a!) y, Tensor pvec, Tensor(b!) dot_partial, "
-        "int W, int m, int col_lo, int row0, int wsize, int rbase, "
-        "int rhi) -> ()");
+        "Tensor hhi, Tensor(a!) y, Tensor pvec, int W, int m, int col_lo, "
+        "int row0, int wsize, int rbase, int rhi) -> Tensor");
   m.def("dia_residual(Tensor dvals, Tensor offs, Tensor hlo, Tensor own, "
         "Tensor hhi, Tensor b, Tensor(a!) y, int W, int m, int col_lo, "
         "int row0, int wsize, int rbase, int rhi) -> ()");
@@ -181,7 +174,6 @@ TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
   m.impl("mult_dense", mult_dense_hip);
   m.impl("axpby", axpby_hip);
   m.impl("spmv_dot", spmv_dot_hip);
-  m.impl("csr_row_spmv", csr_row_spmv_hip);
   m.impl("axpby_norm2", axpby_norm2_hip);
   m.impl("build_ell", build_ell_hip);
   m.impl("build_dia", build_dia_hip);

@@ -16,6 +16,11 @@
 //    a tiny fixup kernel (atomic-free main path);
 //  - optional fused dot accumulates sum(p[r]*y[r]) per block (CG p·Ap);
 //    the fixup kernel reduces the per-block partials.
+//
+// Below it: the padded-ELL and device-DIA mirrors and their row-pair kernel
+// family (ell_spmv, ell_jacobi, dia_spmv incl. the residual, dia_jacobi,
+// dia_spmv_bpdot), which share one window view, one accumulate loop per
+// format, one block reduction and one host launch helper.
 #include <type_traits>
 
 #include "common.h"
@@ -30,6 +35,23 @@ template <typename U>
 struct alignas(4 * sizeof(U) <= 16 ? 4 * sizeof(U) : 16) Quad {
   U v[4];
 };
+
+// adjacent pair: one 2-element vector load / store per stream
+template <typename U>
+struct alignas(2 * sizeof(U) <= 16 ? 2 * sizeof(U) : 16) Pair {
+  U a, b;
+};
+
+// 256-thread LDS tree sum of red[0..BLK) into red[0].  Every thread of the
+// block must call it, with its own red[tid] already written.
+template <typename T>
+__device__ __forceinline__ void block_reduce_sum(T* red, int tid) {
+  __syncthreads();
+  for (int w = BLK / 2; w > 0; w >>= 1) {
+    if (tid < w) red[tid] += red[tid + w];
+    __syncthreads();
+  }
+}
 
 template <typename T, typename index_t, bool BETA_ZERO, bool FUSE_DOT>
 __global__ __launch_bounds__(BLK) void spmv_kernel(
@@ -123,11 +145,7 @@ __global__ __launch_bounds__(BLK) void spmv_kernel(
       T acc = ZeroOf<T>::value();
       for (int64_t p = s + tid; p < cend; p += BLK) acc += prod[p - s];
       red[tid] = acc;
-      __syncthreads();
-      for (int w = BLK / 2; w > 0; w >>= 1) {
-        if (tid < w) red[tid] += red[tid + w];
-        __syncthreads();
-      }
+      block_reduce_sum(red, tid);
       if (tid == 0) {
         carry_val[b] = red[0];
         carry_row[b] = ro0 - 1;
@@ -139,11 +157,7 @@ __global__ __launch_bounds__(BLK) void spmv_kernel(
   if (FUSE_DOT) {
     __syncthreads();
     red[tid] = dacc;
-    __syncthreads();
-    for (int w = BLK / 2; w > 0; w >>= 1) {
-      if (tid < w) red[tid] += red[tid + w];
-      __syncthreads();
-    }
+    block_reduce_sum(red, tid);
     // per-block partial; one atomic per address would serialize at 163k
     // blocks, so the fixup kernel reduces these (nblocks/256 atomics).
     if (tid == 0) dot_partial[b] = red[0];
@@ -157,7 +171,7 @@ __global__ void carry_fixup_kernel(const T* __restrict__ carry_val,
                                    const T* __restrict__ pvec,
                                    const T* __restrict__ dot_partial,
                                    T* __restrict__ dot_out) {
-  __shared__ __align__(16) char red_raw[256 * sizeof(T)];
+  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
   T* red = reinterpret_cast<T*>(red_raw);
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   T dacc = ZeroOf<T>::value();
@@ -172,11 +186,7 @@ __global__ void carry_fixup_kernel(const T* __restrict__ carry_val,
   }
   if (FUSE_DOT) {
     red[threadIdx.x] = dacc;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
+    block_reduce_sum(red, (int)threadIdx.x);
     if (threadIdx.x == 0) atomic_add_any(dot_out, red[0]);
   }
 }
@@ -323,105 +333,334 @@ __global__ void build_dia_kernel(const int64_t* __restrict__ indptr,
   }
 }
 
-// nt_load (common.h): measured on the 16384^2 5-pt DIA SpMV:
-// 2.580 -> 2.474 ms (tools/dia_nt_bench.hip); nt STORES measured slower,
-// so outputs use plain stores.
 
-// Window pair load [c0, c0+1] from a single piece (SINGLE mode), clamped
-// at the edges.  Rows r0, r0+1 of one thread access consecutive columns on
-// every diagonal, and the alignment parity (c0 & 1) is uniform per
-// diagonal (r0 is even), so the interior fast path is one 16B load (even
-// parity) or two scalars (odd) — halving the load-issue count that bounds
-// the DIA kernels (profiled 4.6 TB/s issue-bound vs 6.0 achievable).
+// ---------------------------------------------------------------------------
+// Row-pair core shared by the ELL and DIA kernels below.  Every thread owns
+// rows r0, r0+1 (r0 even) and walks the W column-major planes; x comes from
+// a window of up to three pieces.  Planes are single-use streams and take
+// nt_load (common.h; measured on the 16384^2 5-pt DIA SpMV: 2.580 -> 2.474
+// ms, tools/dia_nt_bench.hip); nt STORES measured slower, so outputs use
+// plain stores.
+
+// x window (halo_lo | own slab | halo_hi) — the own piece is the rank's x
+// slab used IN PLACE (no per-SpMV self-copy).  SINGLE: the whole window is
+// the own slab (ws=1 fast case) — no piece branch.
 template <typename T>
-__device__ __forceinline__ void wpair(const T* __restrict__ v, int64_t c0,
-                                      int64_t wsize, T& o0, T& o1) {
-  if (c0 >= 0 && c0 + 1 < wsize) {
-    if ((c0 & 1) == 0) {
-      struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-      const TP t = *reinterpret_cast<const TP*>(&v[c0]);
-      o0 = t.a;
-      o1 = t.b;
+struct XWindow {
+  const T* hlo;
+  const T* own;
+  const T* hhi;
+  int64_t nlo, nown, wsize;
+
+  // gather at window-relative index idx (ELL)
+  template <bool SINGLE>
+  __device__ __forceinline__ T at(int64_t idx) const {
+    if (SINGLE) return own[idx];
+    if (idx < nlo) return hlo[idx];
+    idx -= nlo;
+    if (idx < nown) return own[idx];
+    return hhi[idx - nown];
+  }
+
+  // adjacent pair [c0, c0+1], clamped at the window edges (DIA: padded
+  // plane entries are 0, so a clamped load is safe).  Rows r0, r0+1 of one
+  // thread access consecutive columns on every diagonal, and the alignment
+  // parity (c0 & 1) is uniform per diagonal (r0 is even), so the SINGLE
+  // interior fast path is one 16B load (even parity) or two scalars (odd) —
+  // halving the load-issue count that bounds the DIA kernels (profiled
+  // 4.6 TB/s issue-bound vs 6.0 achievable).
+  template <bool SINGLE>
+  __device__ __forceinline__ void pair(int64_t c0, T& x0, T& x1) const {
+    if (SINGLE) {
+      if (c0 >= 0 && c0 + 1 < wsize) {
+        if ((c0 & 1) == 0) {
+          const Pair<T> t = *reinterpret_cast<const Pair<T>*>(&own[c0]);
+          x0 = t.a;
+          x1 = t.b;
+        } else {
+          x0 = own[c0];
+          x1 = own[c0 + 1];
+        }
+      } else {
+        x0 = own[min(max(c0, (int64_t)0), wsize - 1)];
+        x1 = own[min(max(c0 + 1, (int64_t)0), wsize - 1)];
+      }
     } else {
-      o0 = v[c0];
-      o1 = v[c0 + 1];
+      x0 = at<false>(min(max(c0, (int64_t)0), wsize - 1));
+      x1 = at<false>(min(max(c0 + 1, (int64_t)0), wsize - 1));
     }
-  } else {
-    o0 = v[min(max(c0, (int64_t)0), wsize - 1)];
-    o1 = v[min(max(c0 + 1, (int64_t)0), wsize - 1)];
+  }
+};
+
+// a0, a1 += sum_k evals[k][r0, r0+1] * x[eidx[k][r0, r0+1] - col_lo]
+template <typename T, typename index_t, bool SINGLE>
+__device__ __forceinline__ void ell_accumulate(
+    const index_t* __restrict__ eidx, const T* __restrict__ evals, int W,
+    int64_t mp, int64_t r0, int64_t col_lo, const XWindow<T>& win, T& a0,
+    T& a1) {
+  for (int k = 0; k < W; ++k) {
+    const int64_t base = (int64_t)k * mp + r0;
+    Pair<index_t> ii;
+    ii.a = nt_load(&eidx[base]);
+    ii.b = nt_load(&eidx[base + 1]);
+    Pair<T> vv;
+    vv.a = nt_load(&evals[base]);
+    vv.b = nt_load(&evals[base + 1]);
+    a0 += vv.a * win.template at<SINGLE>((int64_t)ii.a - col_lo);
+    a1 += vv.b * win.template at<SINGLE>((int64_t)ii.b - col_lo);
   }
 }
 
-// window-relative x lookup over (halo_lo | own slab | halo_hi) — the own
-// piece is the rank's x slab used IN PLACE (no per-SpMV self-copy).
-template <typename T>
-__device__ __forceinline__ T xpiece(int64_t idx, const T* __restrict__ hlo,
-                                    int64_t nlo, const T* __restrict__ own,
-                                    int64_t nown, const T* __restrict__ hhi) {
-  if (idx < nlo) return hlo[idx];
-  idx -= nlo;
-  if (idx < nown) return own[idx];
-  return hhi[idx - nown];
+// a0, a1 += sum_k dvals[k][r0, r0+1] * xpair(cbase + offs[k]); cbase is the
+// window-relative column of row r0 on the main diagonal and xpair(c0, x0,
+// x1) yields the x pair at window columns c0, c0+1.
+template <typename T, typename XPair>
+__device__ __forceinline__ void dia_accumulate(
+    const T* __restrict__ dvals, const int64_t* __restrict__ offs, int W,
+    int64_t mp, int64_t r0, int64_t cbase, XPair xpair, T& a0, T& a1) {
+  for (int k = 0; k < W; ++k) {
+    const int64_t base = (int64_t)k * mp + r0;
+    Pair<T> vv;
+    vv.a = nt_load(&dvals[base]);
+    vv.b = nt_load(&dvals[base + 1]);
+    T x0, x1;
+    xpair(cbase + offs[k], x0, x1);
+    a0 += vv.a * x0;
+    a1 += vv.b * x1;
+  }
 }
 
+// rows r0, r0+1 of an output: one pair store, or the lone tail row
+template <typename T>
+__device__ __forceinline__ void store_pair_or_tail(T* __restrict__ dst,
+                                                   int64_t r0, int64_t m,
+                                                   int64_t rhi, T v0, T v1) {
+  if (r0 + 1 < min(m, rhi)) {
+    *reinterpret_cast<Pair<T>*>(&dst[r0]) = Pair<T>{v0, v1};
+  } else if (r0 < m) {
+    dst[r0] = v0;
+  }
+}
+
+// x_out = x + omega * dinv * (b - A x) for rows r0, r0+1 (a0, a1 = A x)
+template <typename T>
+__device__ __forceinline__ void jacobi_update(
+    const T* __restrict__ xloc, const T* __restrict__ b,
+    const T* __restrict__ dinv, T* __restrict__ xout, T omega, int64_t r0,
+    int64_t m, int64_t rhi, T a0, T a1) {
+  if (r0 + 1 < min(m, rhi)) {
+    const Pair<T> xv = *reinterpret_cast<const Pair<T>*>(&xloc[r0]);
+    const Pair<T> bv = *reinterpret_cast<const Pair<T>*>(&b[r0]);
+    const Pair<T> dv = *reinterpret_cast<const Pair<T>*>(&dinv[r0]);
+    *reinterpret_cast<Pair<T>*>(&xout[r0]) =
+        Pair<T>{xv.a + omega * dv.a * (bv.a - a0),
+                xv.b + omega * dv.b * (bv.b - a1)};
+  } else if (r0 < m) {
+    xout[r0] = xloc[r0] + omega * dinv[r0] * (b[r0] - a0);
+  }
+}
+
+// fused-dot epilogue: every thread of the block contributes d; slot
+// blockIdx.x of dot_partial receives the block sum
+template <typename T>
+__device__ __forceinline__ void block_dot_partial(T* red, T d,
+                                                  T* __restrict__ dot_partial) {
+  red[threadIdx.x] = d;
+  block_reduce_sum(red, (int)threadIdx.x);
+  if (threadIdx.x == 0) dot_partial[blockIdx.x] = red[0];
+}
+
+// [rbase, rhi): row sub-range (rbase even) — the interior/boundary split
+// that overlaps halo exchange with interior compute at ws>1 (ell_spmv,
+// dia_spmv, dia_jacobi share this contract)
 template <typename T, typename index_t, bool FUSE_DOT, bool SINGLE>
 __global__ __launch_bounds__(BLK) void ell_spmv_kernel(
     const index_t* __restrict__ eidx, const T* __restrict__ evals,
-    const T* __restrict__ hlo, const T* __restrict__ own,
-    const T* __restrict__ hhi, T* __restrict__ y,
-    const T* __restrict__ pvec, T* __restrict__ dot_partial,
-    int64_t m, int64_t mp, int W, int64_t col_lo, int64_t nlo, int64_t nown,
+    const XWindow<T> win, T* __restrict__ y, const T* __restrict__ pvec,
+    T* __restrict__ dot_partial, int64_t m, int64_t mp, int W, int64_t col_lo,
     int64_t rbase, int64_t rhi) {
-  // [rbase, rhi): row sub-range (rbase even) — the interior/boundary split
-  // that overlaps halo exchange with interior compute at ws>1 (same
-  // contract as dia_spmv_kernel)
   __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
-  T* red = reinterpret_cast<T*>(red_raw);
-  const int64_t t = (int64_t)blockIdx.x * BLK + threadIdx.x;
-  const int64_t r0 = rbase + 2 * t;
+  const int64_t r0 = rbase + 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
   T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
   if (r0 < rhi) {
-    for (int k = 0; k < W; ++k) {
-      const int64_t base = (int64_t)k * mp + r0;
-      // adjacent pair: one 2-element vector load per stream
-      struct alignas(2 * sizeof(index_t) <= 16 ? 2 * sizeof(index_t) : 16) IP { index_t a, b; };
-      struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-      IP ii;
-      ii.a = nt_load(&eidx[base]);
-      ii.b = nt_load(&eidx[base + 1]);
-      TP vv;
-      vv.a = nt_load(&evals[base]);
-      vv.b = nt_load(&evals[base + 1]);
-      if (SINGLE) {
-        // ws=1 fast case: the whole window is the own slab — no piece branch
-        a0 += vv.a * own[(int64_t)ii.a - col_lo];
-        a1 += vv.b * own[(int64_t)ii.b - col_lo];
-      } else {
-        a0 += vv.a * xpiece((int64_t)ii.a - col_lo, hlo, nlo, own, nown, hhi);
-        a1 += vv.b * xpiece((int64_t)ii.b - col_lo, hlo, nlo, own, nown, hhi);
-      }
-    }
-    if (r0 + 1 < min(m, rhi)) {
-      struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-      TP out{a0, a1};
-      *reinterpret_cast<TP*>(&y[r0]) = out;
+    ell_accumulate<T, index_t, SINGLE>(eidx, evals, W, mp, r0, col_lo, win,
+                                       a0, a1);
+    store_pair_or_tail(y, r0, m, rhi, a0, a1);
+  }
+  if (FUSE_DOT) {
+    T d = ZeroOf<T>::value();
+    if (r0 < min(m, rhi)) d += a0 * pvec[r0];
+    if (r0 + 1 < min(m, rhi)) d += a1 * pvec[r0 + 1];
+    block_dot_partial(reinterpret_cast<T*>(red_raw), d, dot_partial);
+  }
+}
+
+// Fused weighted-Jacobi sweep on the ELL mirror:
+//   x_out[r] = x[r] + omega * dinv[r] * (b[r] - (A x)[r])
+// One pass over A + 4 vector streams instead of spmv + 2 elementwise
+// kernels (the GMG/AMG smoother, reference WeightedJacobi gmg.py:247-285).
+template <typename T, typename index_t, bool SINGLE>
+__global__ __launch_bounds__(BLK) void ell_jacobi_kernel(
+    const index_t* __restrict__ eidx, const T* __restrict__ evals,
+    const XWindow<T> win, const T* __restrict__ xloc,
+    const T* __restrict__ b, const T* __restrict__ dinv,
+    T* __restrict__ xout, int64_t m, int64_t mp, int W, int64_t col_lo,
+    T omega) {
+  const int64_t r0 = 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
+  if (r0 >= mp) return;
+  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
+  ell_accumulate<T, index_t, SINGLE>(eidx, evals, W, mp, r0, col_lo, win, a0,
+                                     a1);
+  jacobi_update(xloc, b, dinv, xout, omega, r0, m, m, a0, a1);
+}
+
+// Device-DIA fast path: when the matrix has few distinct diagonals
+// (col - row values), store ONLY the padded value planes column-major plus
+// the W offsets — the index stream disappears (12 -> 8 B/nnz for
+// fp64+int32).  Invalid/padded entries hold 0 and their x loads are clamped
+// into the window.  Reference context: the dia format (sparse/dia.py) is a
+// host/conversion format there; here it is the SpMV execution format for
+// banded operators (Poisson, dot_microbenchmark).
+template <typename T, bool FUSE_DOT, bool SINGLE, bool RESID = false>
+__global__ __launch_bounds__(BLK) void dia_spmv_kernel(
+    const T* __restrict__ dvals,  // (W, mp) column-major planes
+    const int64_t* __restrict__ offs,  // W diagonal offsets
+    const XWindow<T> win, T* __restrict__ y, const T* __restrict__ pvec,
+    T* __restrict__ dot_partial, int64_t m, int64_t mp, int W, int64_t col_lo,
+    int64_t row0, int64_t rbase, int64_t rhi) {
+  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
+  const int64_t r0 = rbase + 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
+  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
+  if (r0 < rhi) {
+    dia_accumulate(
+        dvals, offs, W, mp, r0, row0 + r0 - col_lo,
+        [&](int64_t c0, T& x0, T& x1) {
+          win.template pair<SINGLE>(c0, x0, x1);
+        },
+        a0, a1);
+    if (!RESID) {
+      store_pair_or_tail(y, r0, m, rhi, a0, a1);
+    } else if (r0 + 1 < min(m, rhi)) {
+      // y = b - A x (pvec carries b): the V-cycle residual fused into
+      // the SpMV — saves the separate 3-pass pointwise kernel
+      const Pair<T> bv = *reinterpret_cast<const Pair<T>*>(&pvec[r0]);
+      *reinterpret_cast<Pair<T>*>(&y[r0]) = Pair<T>{bv.a - a0, bv.b - a1};
     } else if (r0 < m) {
-      y[r0] = a0;
+      y[r0] = pvec[r0] - a0;
     }
   }
   if (FUSE_DOT) {
     T d = ZeroOf<T>::value();
     if (r0 < min(m, rhi)) d += a0 * pvec[r0];
     if (r0 + 1 < min(m, rhi)) d += a1 * pvec[r0 + 1];
-    red[threadIdx.x] = d;
-    __syncthreads();
-    for (int w = BLK / 2; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) dot_partial[blockIdx.x] = red[0];
+    block_dot_partial(reinterpret_cast<T*>(red_raw), d, dot_partial);
   }
 }
+
+template <typename T, bool SINGLE>
+__global__ __launch_bounds__(BLK) void dia_jacobi_kernel(
+    const T* __restrict__ dvals, const int64_t* __restrict__ offs,
+    const XWindow<T> win, const T* __restrict__ xloc,
+    const T* __restrict__ b, const T* __restrict__ dinv,
+    T* __restrict__ xout, int64_t m, int64_t mp, int W, int64_t col_lo,
+    int64_t row0, T omega, int64_t rbase, int64_t rhi) {
+  const int64_t r0 = rbase + 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
+  if (r0 >= rhi) return;
+  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
+  dia_accumulate(
+      dvals, offs, W, mp, r0, row0 + r0 - col_lo,
+      [&](int64_t c0, T& x0, T& x1) { win.template pair<SINGLE>(c0, x0, x1); },
+      a0, a1);
+  jacobi_update(xloc, b, dinv, xout, omega, r0, m, rhi, a0, a1);
+}
+
+// Fully-fused CG K1 on the DIA mirror (two-kernel CG iteration):
+//   p_new = r + beta * p_old   (beta = *beta_num / *beta_den, device scalars)
+//   q     = A p_new
+//   pq    = p_new . q          (per-block partials)
+// p_new at neighbor columns is recomputed on the fly from the r / p_old
+// windows (deterministic IEEE => identical to the stored value), so the
+// separate p-update pass over 3 vector streams disappears.  p_old and
+// p_new MUST be distinct buffers (double-buffered by the caller).
+// Reference context: this is the MI355X fusion of the reference CG loop's
+// AXPBY + SpMV + dot task chain (linalg.py:499-565).
+template <typename T, bool SINGLE>
+__global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
+    const T* __restrict__ dvals, const int64_t* __restrict__ offs,
+    const XWindow<T> rwin, const XWindow<T> pwin, T* __restrict__ pnew,
+    T* __restrict__ q, const T* __restrict__ beta_num,
+    const T* __restrict__ beta_den, T* __restrict__ dot_partial, int64_t m,
+    int64_t mp, int W, int64_t col_lo, int64_t row0) {
+  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
+  const T beta = (*beta_num) / (*beta_den);
+  const int64_t r0 = 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
+  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
+  T p0 = ZeroOf<T>::value(), p1 = ZeroOf<T>::value();
+  if (r0 < mp) {
+    auto pnew_pair = [&](int64_t c0, T& x0, T& x1) {
+      T r0v, r1v, p0v, p1v;
+      rwin.template pair<SINGLE>(c0, r0v, r1v);
+      pwin.template pair<SINGLE>(c0, p0v, p1v);
+      x0 = r0v + beta * p0v;
+      x1 = r1v + beta * p1v;
+    };
+    // window index of own row r0: row0 - col_lo + r0
+    const int64_t cbase = row0 + r0 - col_lo;
+    dia_accumulate(dvals, offs, W, mp, r0, cbase, pnew_pair, a0, a1);
+    // own-row p_new (same formula as the window recompute => identical fp);
+    // p1 of a lone tail row is a clamped load that is never used
+    pnew_pair(cbase, p0, p1);
+    store_pair_or_tail(pnew, r0, m, m, p0, p1);
+    store_pair_or_tail(q, r0, m, m, a0, a1);
+  }
+  T d = ZeroOf<T>::value();
+  if (r0 < m) d += a0 * p0;
+  if (r0 + 1 < m) d += a1 * p1;
+  block_dot_partial(reinterpret_cast<T*>(red_raw), d, dot_partial);
+}
+
+// blocks of BLK threads covering `span` rows, two rows per thread
+inline int64_t pair_blocks(int64_t span) {
+  return (span + 2 * BLK - 1) / (2 * BLK);
+}
+
+template <typename F>
+void dispatch_bool(bool v, F&& f) {
+  if (v) f(std::true_type{}); else f(std::false_type{});
+}
+
+// Launch geometry shared by every row-pair launcher: padded row count, the
+// resolved row range (rhi < 0 = all rows), window piece sizes and the grid.
+struct RowPairLaunch {
+  int64_t mp, rbase, rhi, nlo, nown, wsize, nblocks;
+  bool single;  // no halo pieces: the own slab is the whole window
+
+  RowPairLaunch(const at::Tensor& planes, int64_t W, const at::Tensor& hlo,
+                const at::Tensor& own, const at::Tensor& hhi, int64_t wsize_,
+                int64_t rbase_ = 0, int64_t rhi_ = -1)
+      : mp(planes.numel() / W), rbase(rbase_), rhi(rhi_ < 0 ? mp : rhi_),
+        nlo(hlo.numel()), nown(own.numel()), wsize(wsize_),
+        nblocks(rhi > rbase ? pair_blocks(rhi - rbase) : 0),
+        single(nlo == 0 && hhi.numel() == 0) {}
+
+  bool empty() const { return nblocks == 0; }
+
+  // window view of one vector's pieces; an empty halo piece is never read,
+  // its pointer only has to be valid
+  template <typename T>
+  XWindow<T> window(const at::Tensor& hlo, const at::Tensor& own,
+                    const at::Tensor& hhi) const {
+    const T* o = own.data_ptr<T>();
+    return {hlo.numel() ? hlo.data_ptr<T>() : o, o,
+            hhi.numel() ? hhi.data_ptr<T>() : o, nlo, nown, wsize};
+  }
+
+  template <typename... P, typename... A>
+  void launch(void (*kern)(P...), A... args) const {
+    hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
+                       static_cast<P>(args)...);
+  }
+};
 
 }  // namespace
 
@@ -438,46 +677,6 @@ void build_ell_hip(at::Tensor indptr, at::Tensor indices, at::Tensor values,
                          indices.data_ptr<index_t>(), values.data_ptr<T>(),
                          eidx.data_ptr<index_t>(), evals.data_ptr<T>(), m, mp,
                          (int)W, (index_t)pad_idx);
-    });
-  });
-}
-
-void ell_spmv_hip(at::Tensor eidx, at::Tensor evals, at::Tensor hlo,
-                  at::Tensor own, at::Tensor hhi, at::Tensor y,
-                  int64_t W, int64_t m, int64_t col_lo,
-                  const c10::optional<at::Tensor>& pvec,
-                  const c10::optional<at::Tensor>& dot_partial,
-                  int64_t rbase, int64_t rhi) {
-  const int64_t mp = evals.numel() / W;
-  if (rhi < 0) rhi = mp;
-  if (rhi <= rbase) return;
-  const bool fuse = pvec.has_value();
-  const int64_t nblocks = ((rhi - rbase) / 2 + BLK - 1) / BLK;
-  const int64_t nlo = hlo.numel();
-  const int64_t nown = own.numel();
-  DISPATCH_VALUES(evals.scalar_type(), "ell_spmv", [&] {
-    using T = scalar_t;
-    DISPATCH_INDEX(eidx.scalar_type(), "ell_spmv_idx", [&] {
-      const T* hlo_p = nlo ? hlo.data_ptr<T>() : own.data_ptr<T>();
-      const T* hhi_p = hhi.numel() ? hhi.data_ptr<T>() : own.data_ptr<T>();
-      const bool single = (nlo == 0 && hhi.numel() == 0);
-      auto launch = [&](auto kern, const T* pv, T* dp) {
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
-                           eidx.data_ptr<index_t>(), evals.data_ptr<T>(),
-                           hlo_p, own.data_ptr<T>(), hhi_p, y.data_ptr<T>(),
-                           pv, dp, m, mp, (int)W, col_lo, nlo, nown,
-                           rbase, rhi);
-      };
-      if (fuse && single)
-        launch(ell_spmv_kernel<T, index_t, true, true>, pvec->data_ptr<T>(),
-               dot_partial->data_ptr<T>());
-      else if (fuse)
-        launch(ell_spmv_kernel<T, index_t, true, false>, pvec->data_ptr<T>(),
-               dot_partial->data_ptr<T>());
-      else if (single)
-        launch(ell_spmv_kernel<T, index_t, false, true>, nullptr, nullptr);
-      else
-        launch(ell_spmv_kernel<T, index_t, false, false>, nullptr, nullptr);
     });
   });
 }
@@ -501,432 +700,130 @@ void build_dia_hip(at::Tensor indptr, at::Tensor indices, at::Tensor values,
   });
 }
 
+// The fused-dot ops own their per-block partials: one slot per launched
+// block, every block writes its slot, and the 0-dim sum is returned (an
+// empty row range is an exact zero).
+static at::Tensor sum_or_zero(const at::Tensor& partial,
+                              const at::Tensor& like) {
+  return partial.defined() ? partial.sum() : at::zeros({}, like.options());
+}
+
+// y = A x on rows [rbase, rhi); with pvec also the partials of pvec . y
+static at::Tensor ell_spmv_impl(const at::Tensor& eidx, const at::Tensor& evals,
+                                const at::Tensor& hlo, const at::Tensor& own,
+                                const at::Tensor& hhi, at::Tensor& y,
+                                const at::Tensor* pvec, int64_t W, int64_t m,
+                                int64_t col_lo, int64_t rbase, int64_t rhi) {
+  const RowPairLaunch L(evals, W, hlo, own, hhi, 0, rbase, rhi);
+  at::Tensor partial;
+  if (L.empty()) return partial;
+  if (pvec) partial = at::empty({L.nblocks}, evals.options());
+  DISPATCH_VALUES(evals.scalar_type(), "ell_spmv", [&] {
+    using T = scalar_t;
+    DISPATCH_INDEX(eidx.scalar_type(), "ell_spmv_idx", [&] {
+      dispatch_bool(pvec != nullptr, [&](auto fuse) {
+        dispatch_bool(L.single, [&](auto single) {
+          L.launch(ell_spmv_kernel<T, index_t, decltype(fuse)::value,
+                                   decltype(single)::value>,
+                   eidx.data_ptr<index_t>(), evals.data_ptr<T>(),
+                   L.window<T>(hlo, own, hhi), y.data_ptr<T>(),
+                   pvec ? pvec->data_ptr<T>() : nullptr,
+                   pvec ? partial.data_ptr<T>() : nullptr, m, L.mp, W, col_lo,
+                   L.rbase, L.rhi);
+        });
+      });
+    });
+  });
+  return partial;
+}
+
 void ell_spmv_plain_hip(at::Tensor eidx, at::Tensor evals, at::Tensor hlo,
                         at::Tensor own, at::Tensor hhi, at::Tensor y,
                         int64_t W, int64_t m, int64_t col_lo,
                         int64_t rbase, int64_t rhi) {
-  ell_spmv_hip(eidx, evals, hlo, own, hhi, y, W, m, col_lo, c10::nullopt,
-               c10::nullopt, rbase, rhi);
+  ell_spmv_impl(eidx, evals, hlo, own, hhi, y, nullptr, W, m, col_lo, rbase,
+                rhi);
 }
 
-void ell_spmv_dot_hip(at::Tensor eidx, at::Tensor evals, at::Tensor hlo,
-                      at::Tensor own, at::Tensor hhi, at::Tensor y,
-                      at::Tensor pvec, at::Tensor dot_partial,
-                      int64_t W, int64_t m, int64_t col_lo,
-                      int64_t rbase, int64_t rhi) {
-  ell_spmv_hip(eidx, evals, hlo, own, hhi, y, W, m, col_lo, pvec, dot_partial,
-               rbase, rhi);
+at::Tensor ell_spmv_dot_hip(at::Tensor eidx, at::Tensor evals, at::Tensor hlo,
+                            at::Tensor own, at::Tensor hhi, at::Tensor y,
+                            at::Tensor pvec, int64_t W, int64_t m,
+                            int64_t col_lo, int64_t rbase, int64_t rhi) {
+  return sum_or_zero(ell_spmv_impl(eidx, evals, hlo, own, hhi, y, &pvec, W, m,
+                                   col_lo, rbase, rhi),
+                     evals);
 }
-
-// ---------------------------------------------------------------------------
-// Fused weighted-Jacobi sweep on the ELL mirror:
-//   x_out[r] = x[r] + omega * dinv[r] * (b[r] - (A x)[r])
-// One pass over A + 4 vector streams instead of spmv + 2 elementwise
-// kernels (the GMG/AMG smoother, reference WeightedJacobi gmg.py:247-285).
-namespace {
-
-template <typename T, typename index_t, bool SINGLE>
-__global__ __launch_bounds__(BLK) void ell_jacobi_kernel(
-    const index_t* __restrict__ eidx, const T* __restrict__ evals,
-    const T* __restrict__ hlo, const T* __restrict__ own,
-    const T* __restrict__ hhi, const T* __restrict__ xloc,
-    const T* __restrict__ b, const T* __restrict__ dinv,
-    T* __restrict__ xout, int64_t m, int64_t mp, int W, int64_t col_lo,
-    int64_t nlo, int64_t nown, T omega) {
-  const int64_t t = (int64_t)blockIdx.x * BLK + threadIdx.x;
-  const int64_t r0 = 2 * t;
-  if (r0 >= mp) return;
-  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
-  for (int k = 0; k < W; ++k) {
-    const int64_t base = (int64_t)k * mp + r0;
-    struct alignas(2 * sizeof(index_t) <= 16 ? 2 * sizeof(index_t) : 16) IP { index_t a, b; };
-    struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-    IP ii;
-    ii.a = nt_load(&eidx[base]);
-    ii.b = nt_load(&eidx[base + 1]);
-    TP vv;
-    vv.a = nt_load(&evals[base]);
-    vv.b = nt_load(&evals[base + 1]);
-    if (SINGLE) {
-      a0 += vv.a * own[(int64_t)ii.a - col_lo];
-      a1 += vv.b * own[(int64_t)ii.b - col_lo];
-    } else {
-      a0 += vv.a * xpiece((int64_t)ii.a - col_lo, hlo, nlo, own, nown, hhi);
-      a1 += vv.b * xpiece((int64_t)ii.b - col_lo, hlo, nlo, own, nown, hhi);
-    }
-  }
-  if (r0 + 1 < m) {
-    struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-    const TP xv = *reinterpret_cast<const TP*>(&xloc[r0]);
-    const TP bv = *reinterpret_cast<const TP*>(&b[r0]);
-    const TP dv = *reinterpret_cast<const TP*>(&dinv[r0]);
-    TP out{xv.a + omega * dv.a * (bv.a - a0),
-           xv.b + omega * dv.b * (bv.b - a1)};
-    *reinterpret_cast<TP*>(&xout[r0]) = out;
-  } else if (r0 < m) {
-    xout[r0] = xloc[r0] + omega * dinv[r0] * (b[r0] - a0);
-  }
-}
-
-}  // namespace
 
 void ell_jacobi_hip(at::Tensor eidx, at::Tensor evals, at::Tensor hlo,
                     at::Tensor own, at::Tensor hhi, at::Tensor xloc,
                     at::Tensor b, at::Tensor dinv, at::Tensor xout,
                     int64_t W, int64_t m, int64_t col_lo, double omega) {
-  const int64_t mp = evals.numel() / W;
-  const int64_t nblocks = (mp / 2 + BLK - 1) / BLK;
-  const int64_t nlo = hlo.numel();
-  const int64_t nown = own.numel();
+  const RowPairLaunch L(evals, W, hlo, own, hhi, 0);
+  if (L.empty()) return;
   DISPATCH_VALUES(evals.scalar_type(), "ell_jacobi", [&] {
     using T = scalar_t;
     DISPATCH_INDEX(eidx.scalar_type(), "ell_jacobi_idx", [&] {
-      const T* hlo_p = nlo ? hlo.data_ptr<T>() : own.data_ptr<T>();
-      const T* hhi_p = hhi.numel() ? hhi.data_ptr<T>() : own.data_ptr<T>();
-      const bool single = (nlo == 0 && hhi.numel() == 0);
-      auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
-                           eidx.data_ptr<index_t>(), evals.data_ptr<T>(),
-                           hlo_p, own.data_ptr<T>(), hhi_p, xloc.data_ptr<T>(),
-                           b.data_ptr<T>(), dinv.data_ptr<T>(),
-                           xout.data_ptr<T>(), m, mp, (int)W, col_lo, nlo,
-                           nown, static_cast<T>(omega));
-      };
-      if (single) launch(ell_jacobi_kernel<T, index_t, true>);
-      else launch(ell_jacobi_kernel<T, index_t, false>);
+      dispatch_bool(L.single, [&](auto single) {
+        L.launch(ell_jacobi_kernel<T, index_t, decltype(single)::value>,
+                 eidx.data_ptr<index_t>(), evals.data_ptr<T>(),
+                 L.window<T>(hlo, own, hhi), xloc.data_ptr<T>(),
+                 b.data_ptr<T>(), dinv.data_ptr<T>(), xout.data_ptr<T>(), m,
+                 L.mp, W, col_lo, omega);
+      });
     });
   });
 }
 
-// ---------------------------------------------------------------------------
-// Row-per-thread CSR SpMV: for short-row matrices that the ELL heuristic
-// rejects (padding blowup), a plain thread-per-row loop measured 3.7 TB/s
-// vs the nnz-split kernel's 3.2 on short rows (tools/spmv_bench.hip v1/v2);
-// the nnz-split kernel remains the choice for long/skewed rows.
-namespace {
-
-template <typename T, typename index_t>
-__global__ __launch_bounds__(BLK) void csr_row_spmv_kernel(
-    const int64_t* __restrict__ indptr, const index_t* __restrict__ indices,
-    const T* __restrict__ vals, const T* __restrict__ x, T* __restrict__ y,
-    int64_t m, int64_t col_lo) {
-  const int64_t b = xcd_swizzle(blockIdx.x, gridDim.x);
-  const int64_t r = b * BLK + threadIdx.x;
-  if (r >= m) return;
-  const int64_t e = indptr[r + 1];
-  T acc = ZeroOf<T>::value();
-  for (int64_t p = indptr[r]; p < e; ++p) {
-    acc += vals[p] * x[(int64_t)indices[p] - col_lo];
-  }
-  y[r] = acc;
-}
-
-}  // namespace
-
-void csr_row_spmv_hip(at::Tensor indptr, at::Tensor indices, at::Tensor values,
-                      at::Tensor x, at::Tensor y, int64_t col_lo) {
-  const int64_t m = indptr.numel() - 1;
-  if (m == 0) return;
-  DISPATCH_VALUES(values.scalar_type(), "csr_row_spmv", [&] {
-    using T = scalar_t;
-    DISPATCH_INDEX(indices.scalar_type(), "csr_row_spmv_idx", [&] {
-      hipLaunchKernelGGL((csr_row_spmv_kernel<T, index_t>),
-                         dim3((m + BLK - 1) / BLK), dim3(BLK), 0, cur_stream(),
-                         indptr.data_ptr<int64_t>(), indices.data_ptr<index_t>(),
-                         values.data_ptr<T>(), x.data_ptr<T>(), y.data_ptr<T>(),
-                         m, col_lo);
-    });
-  });
-}
-
-// ---------------------------------------------------------------------------
-// Device-DIA fast path: when the matrix has few distinct diagonals
-// (col - row values), store ONLY the padded value planes column-major plus
-// the W offsets — the index stream disappears (12 -> 8 B/nnz for
-// fp64+int32).  Invalid/padded entries hold 0 and their x loads are clamped
-// into the window.  Reference context: the dia format (sparse/dia.py) is a
-// host/conversion format there; here it is the SpMV execution format for
-// banded operators (Poisson, dot_microbenchmark).
-namespace {
-
-template <typename T, bool FUSE_DOT, bool SINGLE, bool RESID = false>
-__global__ __launch_bounds__(BLK) void dia_spmv_kernel(
-    const T* __restrict__ dvals,  // (W, mp) column-major planes
-    const int64_t* __restrict__ offs,  // W diagonal offsets
-    const T* __restrict__ hlo, const T* __restrict__ own,
-    const T* __restrict__ hhi, T* __restrict__ y,
-    const T* __restrict__ pvec, T* __restrict__ dot_partial,
-    int64_t m, int64_t mp, int W, int64_t col_lo, int64_t row0,
-    int64_t nlo, int64_t nown, int64_t wsize, int64_t rbase, int64_t rhi) {
-  // [rbase, rhi): row sub-range (rbase even) — the interior/boundary split
-  // that overlaps halo exchange with interior compute at ws>1
-  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
-  T* red = reinterpret_cast<T*>(red_raw);
-  const int64_t t = (int64_t)blockIdx.x * BLK + threadIdx.x;
-  const int64_t r0 = rbase + 2 * t;
-  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
-  if (r0 < rhi) {
-    for (int k = 0; k < W; ++k) {
-      const int64_t base = (int64_t)k * mp + r0;
-      struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-      TP vv;
-      vv.a = nt_load(&dvals[base]);
-      vv.b = nt_load(&dvals[base + 1]);
-      // window-relative column; padded entries are 0 so a clamped load is safe
-      const int64_t c0 = row0 + r0 + offs[k] - col_lo;
-      if (SINGLE) {
-        T x0, x1;
-        wpair(own, c0, wsize, x0, x1);
-        a0 += vv.a * x0;
-        a1 += vv.b * x1;
-      } else {
-        const int64_t i0 = min(max(c0, (int64_t)0), wsize - 1);
-        const int64_t i1 = min(max(c0 + 1, (int64_t)0), wsize - 1);
-        a0 += vv.a * xpiece(i0, hlo, nlo, own, nown, hhi);
-        a1 += vv.b * xpiece(i1, hlo, nlo, own, nown, hhi);
-      }
-    }
-    if (r0 + 1 < min(m, rhi)) {
-      struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-      TP out{a0, a1};
-      if (RESID) {
-        // y = b - A x (pvec carries b): the V-cycle residual fused into
-        // the SpMV — saves the separate 3-pass pointwise kernel
-        const TP bv = *reinterpret_cast<const TP*>(&pvec[r0]);
-        out.a = bv.a - a0;
-        out.b = bv.b - a1;
-      }
-      *reinterpret_cast<TP*>(&y[r0]) = out;
-    } else if (r0 < m) {
-      y[r0] = RESID ? (pvec[r0] - a0) : a0;
-    }
-  }
-  if (FUSE_DOT) {
-    T d = ZeroOf<T>::value();
-    if (r0 < min(m, rhi)) d += a0 * pvec[r0];
-    if (r0 + 1 < min(m, rhi)) d += a1 * pvec[r0 + 1];
-    red[threadIdx.x] = d;
-    __syncthreads();
-    for (int w = BLK / 2; w > 0; w >>= 1) {
-      if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) dot_partial[blockIdx.x] = red[0];
-  }
-}
-
-template <typename T, bool SINGLE>
-__global__ __launch_bounds__(BLK) void dia_jacobi_kernel(
-    const T* __restrict__ dvals, const int64_t* __restrict__ offs,
-    const T* __restrict__ hlo, const T* __restrict__ own,
-    const T* __restrict__ hhi, const T* __restrict__ xloc,
-    const T* __restrict__ b, const T* __restrict__ dinv,
-    T* __restrict__ xout, int64_t m, int64_t mp, int W, int64_t col_lo,
-    int64_t row0, int64_t nlo, int64_t nown, int64_t wsize, T omega,
-    int64_t rbase, int64_t rhi) {
-  const int64_t t = (int64_t)blockIdx.x * BLK + threadIdx.x;
-  const int64_t r0 = rbase + 2 * t;
-  if (r0 >= rhi) return;
-  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
-  for (int k = 0; k < W; ++k) {
-    const int64_t base = (int64_t)k * mp + r0;
-    struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-    TP vv;
-    vv.a = nt_load(&dvals[base]);
-    vv.b = nt_load(&dvals[base + 1]);
-    const int64_t c0 = row0 + r0 + offs[k] - col_lo;
-    if (SINGLE) {
-      T x0, x1;
-      wpair(own, c0, wsize, x0, x1);
-      a0 += vv.a * x0;
-      a1 += vv.b * x1;
-    } else {
-      const int64_t i0 = min(max(c0, (int64_t)0), wsize - 1);
-      const int64_t i1 = min(max(c0 + 1, (int64_t)0), wsize - 1);
-      a0 += vv.a * xpiece(i0, hlo, nlo, own, nown, hhi);
-      a1 += vv.b * xpiece(i1, hlo, nlo, own, nown, hhi);
-    }
-  }
-  if (r0 + 1 < min(m, rhi)) {
-    struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-    const TP xv = *reinterpret_cast<const TP*>(&xloc[r0]);
-    const TP bv = *reinterpret_cast<const TP*>(&b[r0]);
-    const TP dv = *reinterpret_cast<const TP*>(&dinv[r0]);
-    TP out{xv.a + omega * dv.a * (bv.a - a0),
-           xv.b + omega * dv.b * (bv.b - a1)};
-    *reinterpret_cast<TP*>(&xout[r0]) = out;
-  } else if (r0 < m) {
-    xout[r0] = xloc[r0] + omega * dinv[r0] * (b[r0] - a0);
-  }
-}
-
-// Fully-fused CG K1 on the DIA mirror (two-kernel CG iteration):
-//   p_new = r + beta * p_old   (beta = *beta_num / *beta_den, device scalars)
-//   q     = A p_new
-//   pq    = p_new . q          (per-block partials)
-// p_new at neighbor columns is recomputed on the fly from the r / p_old
-// windows (deterministic IEEE => identical to the stored value), so the
-// separate p-update pass over 3 vector streams disappears.  p_old and
-// p_new MUST be distinct buffers (double-buffered by the caller).
-// Reference context: this is the MI355X fusion of the reference CG loop's
-// AXPBY + SpMV + dot task chain (linalg.py:499-565).
-template <typename T, bool SINGLE>
-__global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
-    const T* __restrict__ dvals, const int64_t* __restrict__ offs,
-    const T* __restrict__ r_hlo, const T* __restrict__ r_own,
-    const T* __restrict__ r_hhi, const T* __restrict__ p_hlo,
-    const T* __restrict__ p_own, const T* __restrict__ p_hhi,
-    T* __restrict__ pnew, T* __restrict__ q,
-    const T* __restrict__ beta_num, const T* __restrict__ beta_den,
-    T* __restrict__ dot_partial, int64_t m, int64_t mp, int W,
-    int64_t col_lo, int64_t row0, int64_t nlo, int64_t nown, int64_t wsize,
-    int64_t own_off) {
-  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
-  T* red = reinterpret_cast<T*>(red_raw);
-  const T beta = (*beta_num) / (*beta_den);
-  const int64_t t = (int64_t)blockIdx.x * BLK + threadIdx.x;
-  const int64_t r0 = 2 * t;
-  T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
-  T p0 = ZeroOf<T>::value(), p1 = ZeroOf<T>::value();
-  if (r0 < mp) {
-    for (int k = 0; k < W; ++k) {
-      const int64_t base = (int64_t)k * mp + r0;
-      T va = nt_load(&dvals[base]);
-      T vb = nt_load(&dvals[base + 1]);
-      const int64_t c0 = row0 + r0 + offs[k] - col_lo;
-      T x0, x1;
-      if (SINGLE) {
-        T r0v, r1v, p0v, p1v;
-        wpair(r_own, c0, wsize, r0v, r1v);
-        wpair(p_own, c0, wsize, p0v, p1v);
-        x0 = r0v + beta * p0v;
-        x1 = r1v + beta * p1v;
-      } else {
-        const int64_t i0 = min(max(c0, (int64_t)0), wsize - 1);
-        const int64_t i1 = min(max(c0 + 1, (int64_t)0), wsize - 1);
-        x0 = xpiece(i0, r_hlo, nlo, r_own, nown, r_hhi)
-             + beta * xpiece(i0, p_hlo, nlo, p_own, nown, p_hhi);
-        x1 = xpiece(i1, r_hlo, nlo, r_own, nown, r_hhi)
-             + beta * xpiece(i1, p_hlo, nlo, p_own, nown, p_hhi);
-      }
-      a0 += va * x0;
-      a1 += vb * x1;
-    }
-    // own-row p_new (same formula as the window recompute => identical fp)
-    const int64_t w0 = own_off + r0;
-    if (SINGLE) {
-      T r0v, r1v, p0v, p1v;
-      wpair(r_own, w0, wsize, r0v, r1v);
-      wpair(p_own, w0, wsize, p0v, p1v);
-      p0 = r0v + beta * p0v;
-      if (r0 + 1 < m) p1 = r1v + beta * p1v;
-    } else {
-      p0 = xpiece(w0, r_hlo, nlo, r_own, nown, r_hhi)
-           + beta * xpiece(w0, p_hlo, nlo, p_own, nown, p_hhi);
-      if (r0 + 1 < m)
-        p1 = xpiece(w0 + 1, r_hlo, nlo, r_own, nown, r_hhi)
-             + beta * xpiece(w0 + 1, p_hlo, nlo, p_own, nown, p_hhi);
-    }
-    if (r0 + 1 < m) {
-      struct alignas(2 * sizeof(T) <= 16 ? 2 * sizeof(T) : 16) TP { T a, b; };
-      TP po{p0, p1};
-      *reinterpret_cast<TP*>(&pnew[r0]) = po;
-      TP qo{a0, a1};
-      *reinterpret_cast<TP*>(&q[r0]) = qo;
-    } else if (r0 < m) {
-      pnew[r0] = p0;
-      q[r0] = a0;
-    }
-  }
-  T d = ZeroOf<T>::value();
-  if (r0 < m) d += a0 * p0;
-  if (r0 + 1 < m) d += a1 * p1;
-  red[threadIdx.x] = d;
-  __syncthreads();
-  for (int w = BLK / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) dot_partial[blockIdx.x] = red[0];
-}
-
-}  // namespace
-
-void dia_spmv_bpdot_hip(at::Tensor dvals, at::Tensor offs, at::Tensor r_hlo,
-                        at::Tensor r_own, at::Tensor r_hhi, at::Tensor p_hlo,
-                        at::Tensor p_own, at::Tensor p_hhi, at::Tensor pnew,
-                        at::Tensor q, at::Tensor beta_num, at::Tensor beta_den,
-                        at::Tensor dot_partial, int64_t W, int64_t m,
-                        int64_t col_lo, int64_t row0, int64_t wsize) {
-  const int64_t mp = dvals.numel() / W;
-  const int64_t nblocks = (mp / 2 + BLK - 1) / BLK;
-  const int64_t nlo = r_hlo.numel();
-  const int64_t nown = r_own.numel();
-  TORCH_CHECK(pnew.data_ptr() != p_own.data_ptr(),
-              "dia_spmv_bpdot: pnew must not alias p_own (double-buffer)");
-  TORCH_CHECK(dot_partial.numel() >= nblocks, "dia_spmv_bpdot: partial small");
-  // own_off: window index of this rank's first own row (row0 - col_lo)
-  const int64_t own_off_w = row0 - col_lo;
-  // in SINGLE mode indices are into the own slab directly
-  const bool single = (nlo == 0 && r_hhi.numel() == 0);
-  DISPATCH_VALUES(dvals.scalar_type(), "dia_spmv_bpdot", [&] {
-    using T = scalar_t;
-    const T* rhlo_p = nlo ? r_hlo.data_ptr<T>() : r_own.data_ptr<T>();
-    const T* rhhi_p = r_hhi.numel() ? r_hhi.data_ptr<T>() : r_own.data_ptr<T>();
-    const T* phlo_p = nlo ? p_hlo.data_ptr<T>() : p_own.data_ptr<T>();
-    const T* phhi_p = p_hhi.numel() ? p_hhi.data_ptr<T>() : p_own.data_ptr<T>();
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
-                         dvals.data_ptr<T>(), offs.data_ptr<int64_t>(),
-                         rhlo_p, r_own.data_ptr<T>(), rhhi_p, phlo_p,
-                         p_own.data_ptr<T>(), phhi_p, pnew.data_ptr<T>(),
-                         q.data_ptr<T>(), beta_num.data_ptr<T>(),
-                         beta_den.data_ptr<T>(), dot_partial.data_ptr<T>(),
-                         m, mp, (int)W, col_lo, row0, nlo, nown, wsize,
-                         own_off_w);
-    };
-    if (single) launch(dia_spmv_bpdot_kernel<T, true>);
-    else launch(dia_spmv_bpdot_kernel<T, false>);
-  });
-}
-
-void dia_spmv_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
-                  at::Tensor own, at::Tensor hhi, at::Tensor y,
-                  int64_t W, int64_t m, int64_t col_lo, int64_t row0,
-                  int64_t wsize,
-                  const c10::optional<at::Tensor>& pvec,
-                  const c10::optional<at::Tensor>& dot_partial,
-                  int64_t rbase, int64_t rhi) {
-  const int64_t mp = dvals.numel() / W;
-  if (rhi < 0) rhi = mp;
-  if (rhi <= rbase) return;
-  const bool fuse = pvec.has_value();
-  const int64_t nblocks = ((rhi - rbase) / 2 + BLK) / BLK;
-  const int64_t nlo = hlo.numel();
-  const int64_t nown = own.numel();
+// y = A x on rows [rbase, rhi); with pvec also the partials of pvec . y;
+// RESID: y = b - A x, the fused V-cycle residual (the pvec slot carries b)
+template <bool RESID>
+static at::Tensor dia_spmv_impl(const at::Tensor& dvals, const at::Tensor& offs,
+                                const at::Tensor& hlo, const at::Tensor& own,
+                                const at::Tensor& hhi, at::Tensor& y,
+                                const at::Tensor* pvec, int64_t W, int64_t m,
+                                int64_t col_lo, int64_t row0, int64_t wsize,
+                                int64_t rbase, int64_t rhi) {
+  const RowPairLaunch L(dvals, W, hlo, own, hhi, wsize, rbase, rhi);
+  const bool fuse_dot = pvec && !RESID;
+  at::Tensor partial;
+  if (L.empty()) return partial;
+  if (fuse_dot) partial = at::empty({L.nblocks}, dvals.options());
   DISPATCH_VALUES(dvals.scalar_type(), "dia_spmv", [&] {
     using T = scalar_t;
-    const T* hlo_p = nlo ? hlo.data_ptr<T>() : own.data_ptr<T>();
-    const T* hhi_p = hhi.numel() ? hhi.data_ptr<T>() : own.data_ptr<T>();
-    const bool single = (nlo == 0 && hhi.numel() == 0);
-    auto launch = [&](auto kern, const T* pv, T* dp) {
-      hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
-                         dvals.data_ptr<T>(), offs.data_ptr<int64_t>(), hlo_p,
-                         own.data_ptr<T>(), hhi_p, y.data_ptr<T>(), pv, dp,
-                         m, mp, (int)W, col_lo, row0, nlo, nown, wsize,
-                         rbase, rhi);
-    };
-    if (fuse && single)
-      launch(dia_spmv_kernel<T, true, true>, pvec->data_ptr<T>(),
-             dot_partial->data_ptr<T>());
-    else if (fuse)
-      launch(dia_spmv_kernel<T, true, false>, pvec->data_ptr<T>(),
-             dot_partial->data_ptr<T>());
-    else if (single)
-      launch(dia_spmv_kernel<T, false, true>, nullptr, nullptr);
-    else
-      launch(dia_spmv_kernel<T, false, false>, nullptr, nullptr);
+    dispatch_bool(fuse_dot, [&](auto fuse) {
+      dispatch_bool(L.single, [&](auto single) {
+        if constexpr (!(RESID && decltype(fuse)::value)) {
+          L.launch(dia_spmv_kernel<T, decltype(fuse)::value,
+                                   decltype(single)::value, RESID>,
+                   dvals.data_ptr<T>(), offs.data_ptr<int64_t>(),
+                   L.window<T>(hlo, own, hhi), y.data_ptr<T>(),
+                   pvec ? pvec->data_ptr<T>() : nullptr,
+                   fuse_dot ? partial.data_ptr<T>() : nullptr, m, L.mp, W,
+                   col_lo, row0, L.rbase, L.rhi);
+        }
+      });
+    });
   });
+  return partial;
+}
+
+void dia_spmv_plain_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
+                        at::Tensor own, at::Tensor hhi, at::Tensor y,
+                        int64_t W, int64_t m, int64_t col_lo, int64_t row0,
+                        int64_t wsize, int64_t rbase, int64_t rhi) {
+  dia_spmv_impl<false>(dvals, offs, hlo, own, hhi, y, nullptr, W, m, col_lo,
+                       row0, wsize, rbase, rhi);
+}
+
+at::Tensor dia_spmv_dot_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
+                            at::Tensor own, at::Tensor hhi, at::Tensor y,
+                            at::Tensor pvec, int64_t W, int64_t m,
+                            int64_t col_lo, int64_t row0, int64_t wsize,
+                            int64_t rbase, int64_t rhi) {
+  return sum_or_zero(dia_spmv_impl<false>(dvals, offs, hlo, own, hhi, y, &pvec,
+                                          W, m, col_lo, row0, wsize, rbase,
+                                          rhi),
+                     dvals);
 }
 
 void dia_residual_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
@@ -934,45 +831,8 @@ void dia_residual_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
                       at::Tensor y, int64_t W, int64_t m, int64_t col_lo,
                       int64_t row0, int64_t wsize, int64_t rbase,
                       int64_t rhi) {
-  // y = b - A x: the fused V-cycle residual (pvec slot carries b)
-  const int64_t mp = dvals.numel() / W;
-  if (rhi < 0) rhi = mp;
-  if (rhi <= rbase) return;
-  const int64_t nblocks = ((rhi - rbase) / 2 + BLK) / BLK;
-  const int64_t nlo = hlo.numel();
-  const int64_t nown = own.numel();
-  DISPATCH_VALUES(dvals.scalar_type(), "dia_residual", [&] {
-    using T = scalar_t;
-    const T* hlo_p = nlo ? hlo.data_ptr<T>() : own.data_ptr<T>();
-    const T* hhi_p = hhi.numel() ? hhi.data_ptr<T>() : own.data_ptr<T>();
-    const bool single = (nlo == 0 && hhi.numel() == 0);
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
-                         dvals.data_ptr<T>(), offs.data_ptr<int64_t>(), hlo_p,
-                         own.data_ptr<T>(), hhi_p, y.data_ptr<T>(),
-                         b.data_ptr<T>(), nullptr, m, mp, (int)W, col_lo,
-                         row0, nlo, nown, wsize, rbase, rhi);
-    };
-    if (single) launch(dia_spmv_kernel<T, false, true, true>);
-    else launch(dia_spmv_kernel<T, false, false, true>);
-  });
-}
-
-void dia_spmv_plain_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
-                        at::Tensor own, at::Tensor hhi, at::Tensor y,
-                        int64_t W, int64_t m, int64_t col_lo, int64_t row0,
-                        int64_t wsize, int64_t rbase, int64_t rhi) {
-  dia_spmv_hip(dvals, offs, hlo, own, hhi, y, W, m, col_lo, row0, wsize,
-               c10::nullopt, c10::nullopt, rbase, rhi);
-}
-
-void dia_spmv_dot_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
-                      at::Tensor own, at::Tensor hhi, at::Tensor y,
-                      at::Tensor pvec, at::Tensor dot_partial, int64_t W,
-                      int64_t m, int64_t col_lo, int64_t row0, int64_t wsize,
-                      int64_t rbase, int64_t rhi) {
-  dia_spmv_hip(dvals, offs, hlo, own, hhi, y, W, m, col_lo, row0, wsize,
-               pvec, dot_partial, rbase, rhi);
+  dia_spmv_impl<true>(dvals, offs, hlo, own, hhi, y, &b, W, m, col_lo, row0,
+                      wsize, rbase, rhi);
 }
 
 void dia_jacobi_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
@@ -980,26 +840,45 @@ void dia_jacobi_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
                     at::Tensor b, at::Tensor dinv, at::Tensor xout,
                     int64_t W, int64_t m, int64_t col_lo, int64_t row0,
                     int64_t wsize, double omega, int64_t rbase, int64_t rhi) {
-  const int64_t mp = dvals.numel() / W;
-  if (rhi < 0) rhi = mp;
-  if (rhi <= rbase) return;
-  const int64_t nblocks = ((rhi - rbase) / 2 + BLK) / BLK;
-  const int64_t nlo = hlo.numel();
-  const int64_t nown = own.numel();
+  const RowPairLaunch L(dvals, W, hlo, own, hhi, wsize, rbase, rhi);
+  if (L.empty()) return;
   DISPATCH_VALUES(dvals.scalar_type(), "dia_jacobi", [&] {
     using T = scalar_t;
-    const T* hlo_p = nlo ? hlo.data_ptr<T>() : own.data_ptr<T>();
-    const T* hhi_p = hhi.numel() ? hhi.data_ptr<T>() : own.data_ptr<T>();
-    const bool single = (nlo == 0 && hhi.numel() == 0);
-    auto launch = [&](auto kern) {
-      hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
-                         dvals.data_ptr<T>(), offs.data_ptr<int64_t>(), hlo_p,
-                         own.data_ptr<T>(), hhi_p, xloc.data_ptr<T>(),
-                         b.data_ptr<T>(), dinv.data_ptr<T>(),
-                         xout.data_ptr<T>(), m, mp, (int)W, col_lo, row0,
-                         nlo, nown, wsize, static_cast<T>(omega), rbase, rhi);
-    };
-    if (single) launch(dia_jacobi_kernel<T, true>);
-    else launch(dia_jacobi_kernel<T, false>);
+    dispatch_bool(L.single, [&](auto single) {
+      L.launch(dia_jacobi_kernel<T, decltype(single)::value>,
+               dvals.data_ptr<T>(), offs.data_ptr<int64_t>(),
+               L.window<T>(hlo, own, hhi), xloc.data_ptr<T>(),
+               b.data_ptr<T>(), dinv.data_ptr<T>(), xout.data_ptr<T>(), m,
+               L.mp, W, col_lo, row0, omega, L.rbase, L.rhi);
+    });
   });
+}
+
+at::Tensor dia_spmv_bpdot_hip(at::Tensor dvals, at::Tensor offs,
+                              at::Tensor r_hlo, at::Tensor r_own,
+                              at::Tensor r_hhi, at::Tensor p_hlo,
+                              at::Tensor p_own, at::Tensor p_hhi,
+                              at::Tensor pnew, at::Tensor q,
+                              at::Tensor beta_num, at::Tensor beta_den,
+                              int64_t W, int64_t m, int64_t col_lo,
+                              int64_t row0, int64_t wsize) {
+  TORCH_CHECK(pnew.data_ptr() != p_own.data_ptr(),
+              "dia_spmv_bpdot: pnew must not alias p_own (double-buffer)");
+  const RowPairLaunch L(dvals, W, r_hlo, r_own, r_hhi, wsize);
+  at::Tensor partial;
+  if (L.empty()) return sum_or_zero(partial, dvals);
+  partial = at::empty({L.nblocks}, dvals.options());
+  DISPATCH_VALUES(dvals.scalar_type(), "dia_spmv_bpdot", [&] {
+    using T = scalar_t;
+    dispatch_bool(L.single, [&](auto single) {
+      L.launch(dia_spmv_bpdot_kernel<T, decltype(single)::value>,
+               dvals.data_ptr<T>(), offs.data_ptr<int64_t>(),
+               L.window<T>(r_hlo, r_own, r_hhi),
+               L.window<T>(p_hlo, p_own, p_hhi), pnew.data_ptr<T>(),
+               q.data_ptr<T>(), beta_num.data_ptr<T>(),
+               beta_den.data_ptr<T>(), partial.data_ptr<T>(), m, L.mp, W,
+               col_lo, row0);
+    });
+  });
+  return partial.sum();
 }

@@ -827,3 +827,198 @@ def test_spgemm_checked_bin_gpu(monkeypatch):
     Cc = ac @ bc
     refc = (a.astype(np.complex128) @ b.astype(np.complex128)).tocsr()
     assert np.allclose(np.asarray(Cc.todense()), refc.toarray(), rtol=1e-10)
+
+
+# -- row-pair DIA/ELL family: pinned behaviour -------------------------------
+# Sizes: a one-row tail thread in a second block (513, 1025), an exact block
+# multiple (512) and odd m with mp = m + 1 (511, 513, 1025).
+_PIN_SIZES = [511, 512, 513, 1025]
+_PIN_DIA_OPS = ["dia_spmv", "dia_spmv_dot", "dia_residual", "dia_jacobi",
+                "dia_spmv_bpdot"]
+_PIN_ELL_OPS = ["ell_spmv", "ell_spmv_dot", "ell_jacobi"]
+_PIN_RANGED_OPS = ["dia_spmv", "dia_spmv_dot", "dia_residual", "dia_jacobi",
+                   "ell_spmv", "ell_spmv_dot"]
+_PIN_OMEGA = 0.7
+_PIN_CACHE = {}
+
+
+class _Pin:
+    """One pinned problem: a scipy matrix with distinct values on every
+    diagonal (DIA) or a row-uniform scattered matrix (ELL), its mirror,
+    seeded vectors and the scipy references of all eight ops."""
+
+    def __init__(self, kind, m, dt):
+        from sparse import csr_array
+
+        rng = np.random.default_rng(7000 + m)
+        if kind == "dia":
+            offs = (-37, -2, 0, 1, 40)
+            s = sps.diags([0.5 + rng.random(m - abs(o)) for o in offs], offs,
+                          shape=(m, m), format="csr")
+        else:
+            W = 8
+            rows = np.repeat(np.arange(m), W)
+            near = (rows + rng.integers(-40, 41, m * W)) % m
+            far = rng.integers(0, m, m * W)
+            cols = np.where(rng.random(m * W) < 0.08, far, near)
+            s = sps.csr_matrix((0.5 + rng.random(m * W), (rows, cols)),
+                               shape=(m, m))
+            s.sum_duplicates()
+        self.s = s = s.astype(dt)
+        self.m, self.dt = m, np.dtype(dt)
+        self.A = A = csr_array(s)
+        if kind == "dia":
+            self.mir = A._dia()
+            assert self.mir is not None
+        else:
+            assert A._dia() is None
+            self.mir = A._ell()
+            assert self.mir is not None
+        self.lo, self.hi = A._col_window()
+        self.w = self.hi - self.lo
+
+        def vec():
+            v = rng.random(m)
+            if self.dt.kind == "c":
+                v = v + 1j * rng.random(m)
+            return v.astype(dt)
+
+        self.np = {k: vec() for k in ("x", "p", "b", "dinv", "r", "pold")}
+        # rows sum at most 8 entries * 1.5 * |x| < 16: with b >= 16 the
+        # residual and the Jacobi update add same-signed terms only, so
+        # the relative tolerances below are not eaten by cancellation
+        self.np["b"] = (self.np["b"] + 16).astype(dt)
+        self.t = {k: torch.as_tensor(v, device="cuda")
+                  for k, v in self.np.items()}
+        tdt = self.t["x"].dtype
+        self.bn = torch.tensor(0.7, device="cuda", dtype=tdt)
+        self.bd = torch.tensor(2.0, device="cuda", dtype=tdt)
+        # references in fp64 / complex128 from the rounded inputs
+        wide = np.complex128 if self.dt.kind == "c" else np.float64
+        n = {k: v.astype(wide) for k, v in self.np.items()}
+        s = s.astype(wide)
+        Ax = s @ n["x"]
+        pn = n["r"] + 0.35 * n["pold"]
+        jac = n["x"] + _PIN_OMEGA * n["dinv"] * (n["b"] - Ax)
+        self.ref = {
+            "spmv": ([Ax], None),
+            "spmv_dot": ([Ax], n["p"] @ Ax),
+            "residual": ([n["b"] - Ax], None),
+            "jacobi": ([jac], None),
+            "spmv_bpdot": ([pn, s @ pn], pn @ (s @ pn)),
+        }
+
+    def pieces(self, name, cut):
+        xw = self.t[name][self.lo:self.hi]
+        if cut is None:
+            return xw[:0], xw, xw[:0]
+        c1, c2 = cut
+        return xw[:c1].clone(), xw[c1:c2].clone(), xw[c2:].clone()
+
+    def new_out(self, op):
+        # NaN-filled: a row no thread wrote fails every comparison
+        k = 2 if op == "dia_spmv_bpdot" else 1
+        return [torch.full((self.m,), float("nan"), dtype=self.t["x"].dtype,
+                           device="cuda") for _ in range(k)]
+
+    def run(self, op, cut=None, rows=(0, -1), out=None):
+        """Run one kernel wrapper; returns (output vectors, dot or None)."""
+        from sparse import kernels as K
+
+        out = self.new_out(op) if out is None else out
+        t, mir, lo, w = self.t, self.mir, self.lo, self.w
+        px = self.pieces("x", cut)
+        dot = None
+        if op == "dia_spmv":
+            K.dia_spmv(mir, px, out[0], lo, w, *rows)
+        elif op == "dia_spmv_dot":
+            dot = K.dia_spmv_dot(mir, px, out[0], t["p"], lo, w, *rows)
+        elif op == "dia_residual":
+            K.dia_residual(mir, px, t["b"], out[0], lo, w, *rows)
+        elif op == "dia_jacobi":
+            K.dia_jacobi(mir, px, t["x"], t["b"], t["dinv"], _PIN_OMEGA,
+                         out[0], lo, w, *rows)
+        elif op == "dia_spmv_bpdot":
+            assert rows == (0, -1)
+            dot = K.dia_spmv_bpdot(mir, self.pieces("r", cut),
+                                   self.pieces("pold", cut), out[0], out[1],
+                                   self.bn, self.bd, lo, w)
+        elif op == "ell_spmv":
+            K.ell_spmv(mir, px, out[0], lo, *rows)
+        elif op == "ell_spmv_dot":
+            dot = K.ell_spmv_dot(mir, px, out[0], t["p"], lo, *rows)
+        elif op == "ell_jacobi":
+            assert rows == (0, -1)
+            K.ell_jacobi(mir, px, t["x"], t["b"], t["dinv"], _PIN_OMEGA,
+                         out[0], lo)
+        else:
+            raise AssertionError(op)
+        return out, dot
+
+
+def _pin(op, m, dt=np.float64):
+    key = (op[:3], m, np.dtype(dt))
+    if key not in _PIN_CACHE:
+        _PIN_CACHE[key] = _Pin(*key)
+    return _PIN_CACHE[key]
+
+
+def _pin_cuts(w):
+    return [(0, w), (1, 2), (101, w - 137), (w // 2, w // 2)]
+
+
+def _pin_check_reference_and_cuts(op, m, dt):
+    P = _pin(op, m, dt)
+    rvecs, rdot = P.ref[op[4:]]
+    vrt = 1e-4 if P.dt == np.float32 else (1e-10 if P.dt.kind == "c"
+                                           else 1e-12)
+    single, sdot = P.run(op)
+    for got, want in zip(single, rvecs):
+        assert np.allclose(got.cpu().numpy(), want, rtol=vrt), (op, m)
+    if rdot is not None:
+        assert sdot.dim() == 0
+        assert np.isclose(float(sdot.item()), float(rdot), rtol=1e-10)
+    for cut in _pin_cuts(P.w):
+        three, tdot = P.run(op, cut=cut)
+        for got, want in zip(three, single):
+            assert torch.equal(got, want), (op, m, cut)
+        if rdot is not None:
+            assert np.isclose(float(tdot.item()), float(rdot), rtol=1e-10)
+
+
+@pytest.mark.parametrize("m", _PIN_SIZES)
+@pytest.mark.parametrize("op", _PIN_DIA_OPS + _PIN_ELL_OPS)
+def test_rowpair_reference_and_window_cuts_gpu(op, m):
+    """Every DIA/ELL row-pair op against scipy, and three-piece x windows
+    (odd cuts hit the odd-parity and clamped pair loads) bit-equal to the
+    single-piece result: the arithmetic per row is identical."""
+    _pin_check_reference_and_cuts(op, m, np.float64)
+
+
+@pytest.mark.parametrize("m", _PIN_SIZES)
+@pytest.mark.parametrize("dt", [np.float32, np.complex128])
+@pytest.mark.parametrize("op", ["dia_spmv", "dia_jacobi"])
+def test_rowpair_dia_dtypes_gpu(op, dt, m):
+    """DIA SpMV and Jacobi in fp32 / complex128 (tolerances as in
+    test_ell_spmv_dtypes_gpu)."""
+    _pin_check_reference_and_cuts(op, m, dt)
+
+
+@pytest.mark.parametrize("m", _PIN_SIZES)
+@pytest.mark.parametrize("op", _PIN_RANGED_OPS)
+def test_rowpair_row_ranges_gpu(op, m):
+    """[a, b), [0, a), [b, -1) with even a < b into one output reproduce
+    the full-range call bit for bit; the split dots sum to the full dot.
+    (0, 512) makes the outer ranges empty at m <= 512 and gives a span
+    whose half is an exact block multiple."""
+    P = _pin(op, m)
+    full, fdot = P.run(op)
+    for a, b in [(2, 258), (0, 512)]:
+        out = P.new_out(op)
+        dots = [P.run(op, rows=rows, out=out)[1]
+                for rows in [(a, b), (0, a), (b, -1)]]
+        assert torch.equal(out[0], full[0]), (op, m, a, b)
+        if fdot is not None:
+            assert all(d.dim() == 0 for d in dots)
+            assert torch.allclose(dots[0] + dots[1] + dots[2], fdot,
+                                  rtol=1e-12, atol=0), (op, m, a, b)
