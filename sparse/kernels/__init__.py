@@ -393,13 +393,26 @@ def cdist(XA, XB, out):
 
 
 # -- device-DIA fast path -----------------------------------------------------
+_DIA_CONST_DTYPES = (torch.float32, torch.float64)
+
+
 class DiaMirror:
-    """Padded diagonal planes of a banded CSR slab: values only, no index
-    stream (12 -> 8 B/nnz for fp64+int32 vs ELL)."""
+    """Diagonal mirror of a banded CSR slab: values only, no index stream.
 
-    __slots__ = ("dvals", "offs", "W", "m", "row0", "off_min", "off_max")
+    Plain: dvals holds the W padded planes, (W, mp) column-major (12 -> 8
+    B/nnz for fp64+int32 vs ELL).
+    Compressed (constant-coefficient stencils): every plane k holds, bit
+    for bit, only +0.0 and one constant, so dvals is None and the mirror
+    keeps cvals (the W constants) and mask (one word per padded row, bit k
+    set where plane k holds cvals[k]; uint8/16/32 for W <= 8/16/32).  The
+    kernels read 1-4 B/row instead of W values and give bit-identical
+    results."""
 
-    def __init__(self, dvals, offs, W, m, row0, off_min=0, off_max=0):
+    __slots__ = ("dvals", "offs", "W", "m", "row0", "off_min", "off_max",
+                 "cvals", "mask")
+
+    def __init__(self, dvals, offs, W, m, row0, off_min=0, off_max=0,
+                 cvals=None, mask=None):
         self.off_min = off_min
         self.off_max = off_max
         self.dvals = dvals
@@ -407,11 +420,25 @@ class DiaMirror:
         self.W = W
         self.m = m
         self.row0 = row0
+        self.cvals = cvals
+        self.mask = mask
+
+    @property
+    def compressed(self) -> bool:
+        return self.mask is not None
+
+    def source(self):
+        """(planes, mask) value-source arguments of the dia_* ops."""
+        if self.compressed:
+            return self.cvals, self.mask
+        return self.dvals, None
 
 
-def build_dia(A, row0: int):
+def build_dia(A, row0: int, compress: bool = True):
     """Build the diagonal mirror of a LocalCSR (cols are GLOBAL; diagonals
-    are col - global_row), or None when not banded enough."""
+    are col - global_row), or None when not banded enough.  The mirror is
+    compressed when its planes classify as constant (DiaMirror), unless
+    compress=False or SPARSE_DIA_NOCOMPRESS=1 asks for the plain one."""
     m = A.nrows
     if m == 0 or A.nnz == 0:
         return None
@@ -441,8 +468,30 @@ def build_dia(A, row0: int):
     # was an nnz-scale indexFuncLargeIndex (~79 ms/call at 931M nnz)
     ext().build_dia(A.indptr, A.indices, A.values, offs.contiguous(), dvals,
                     W, int(row0))
+    cvals = mask = None
+    if (compress and W <= 32 and dvals.dtype in _DIA_CONST_DTYPES
+            and os.environ.get("SPARSE_DIA_NOCOMPRESS") != "1"):
+        # exact, bitwise classification: one extra pass over the planes and
+        # one host read, here at mirror build only.  The decision is local
+        # to this rank's slab and changes no collective (only which value
+        # source the local kernels read), so ranks may safely differ.
+        # The planes are filled first and released after: peak memory of
+        # the build (and the headroom check above) is that of the plain
+        # mirror, and a non-compressible mirror pays the pass and the
+        # short-lived mask too.
+        cvals = torch.zeros(W, dtype=dvals.dtype, device=A.device)
+        mdt = (torch.uint8 if W <= 8 else
+               torch.uint16 if W <= 16 else torch.uint32)
+        mask = torch.empty(mp, dtype=mdt, device=A.device)
+        ok = torch.ones(1, dtype=torch.int32, device=A.device)
+        ext().dia_classify(dvals, cvals, mask, ok, W)
+        if int(ok.item()):
+            dvals = None  # releases the planes
+        else:
+            cvals = mask = None
     return DiaMirror(dvals, offs, W, m, row0,
-                     off_min=int(offs[0].item()), off_max=int(offs[-1].item()))
+                     off_min=int(offs[0].item()), off_max=int(offs[-1].item()),
+                     cvals=cvals, mask=mask)
 
 
 def _pieces(p):
@@ -456,7 +505,7 @@ def dia_spmv(dm: DiaMirror, pieces, y, col_lo: int, wsize: int,
     """rbase/rhi select a row sub-range (rbase even; -1 = all rows): the
     interior/boundary split that overlaps halo exchange with interior
     compute at ws>1."""
-    ext().dia_spmv(dm.dvals, dm.offs, *_pieces(pieces), y, dm.W, dm.m,
+    ext().dia_spmv(*dm.source(), dm.offs, *_pieces(pieces), y, dm.W, dm.m,
                    int(col_lo), dm.row0, int(wsize), int(rbase), int(rhi))
 
 
@@ -464,7 +513,7 @@ def dia_spmv_dot(dm: DiaMirror, pieces, y, p, col_lo: int, wsize: int,
                  rbase: int = 0, rhi: int = -1):
     """Fused y = A@x ; returns sum(p * y) over the row range (device
     0-dim, local partial-sum; exact zero for an empty range)."""
-    return ext().dia_spmv_dot(dm.dvals, dm.offs, *_pieces(pieces), y, p,
+    return ext().dia_spmv_dot(*dm.source(), dm.offs, *_pieces(pieces), y, p,
                               dm.W, dm.m, int(col_lo), dm.row0, int(wsize),
                               int(rbase), int(rhi))
 
@@ -475,7 +524,7 @@ def dia_spmv_bpdot(dm: DiaMirror, r_pieces, p_pieces, pnew, q,
     returns p.q (device 0-dim, local partial-sum).  r_pieces/p_pieces are
     the (hlo, own, hhi) window pieces of r and p_old; pnew must be a
     distinct buffer from p_old (double-buffered caller)."""
-    return ext().dia_spmv_bpdot(dm.dvals, dm.offs, *_pieces(r_pieces),
+    return ext().dia_spmv_bpdot(*dm.source(), dm.offs, *_pieces(r_pieces),
                                 *_pieces(p_pieces), pnew, q, beta_num,
                                 beta_den, dm.W, dm.m, int(col_lo), dm.row0,
                                 int(wsize))
@@ -497,14 +546,15 @@ def cg_xr_norm2(x, p, r, q, a, b):
 def dia_residual(dm: DiaMirror, pieces, b, y, col_lo: int, wsize: int,
                  rbase: int = 0, rhi: int = -1):
     """Fused V-cycle residual y = b - A@x (x given as window pieces)."""
-    ext().dia_residual(dm.dvals, dm.offs, *_pieces(pieces), b, y, dm.W, dm.m,
-                       int(col_lo), dm.row0, int(wsize), int(rbase), int(rhi))
+    ext().dia_residual(*dm.source(), dm.offs, *_pieces(pieces), b, y, dm.W,
+                       dm.m, int(col_lo), dm.row0, int(wsize), int(rbase),
+                       int(rhi))
 
 
 def dia_jacobi(dm: DiaMirror, pieces, xloc, b, dinv, omega, xout,
                col_lo: int, wsize: int, rbase: int = 0, rhi: int = -1):
-    ext().dia_jacobi(dm.dvals, dm.offs, *_pieces(pieces), xloc, b, dinv, xout,
-                     dm.W, dm.m, int(col_lo), dm.row0, int(wsize),
+    ext().dia_jacobi(*dm.source(), dm.offs, *_pieces(pieces), xloc, b, dinv,
+                     xout, dm.W, dm.m, int(col_lo), dm.row0, int(wsize),
                      float(omega), int(rbase), int(rhi))
 
 

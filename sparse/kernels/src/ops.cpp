@@ -28,21 +28,26 @@ void ell_jacobi_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, int64_t, int64_t, int64_t, double);
 void cg_xr_norm2_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                      at::Tensor, at::Tensor, at::Tensor);
-at::Tensor dia_spmv_bpdot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+// DIA ops: (planes, mask) is the value source — the streamed planes and no
+// mask, or the W plane constants and the row mask words
+using OptTensor = c10::optional<at::Tensor>;
+void dia_classify_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, int64_t);
+at::Tensor dia_spmv_bpdot_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
                               at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                               at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                              int64_t, int64_t, int64_t, int64_t, int64_t);
-void dia_spmv_plain_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                        at::Tensor, at::Tensor, int64_t, int64_t, int64_t,
-                        int64_t, int64_t, int64_t, int64_t);
-at::Tensor dia_spmv_dot_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                            at::Tensor, at::Tensor, at::Tensor, int64_t,
+                              at::Tensor, int64_t, int64_t, int64_t, int64_t,
+                              int64_t);
+void dia_spmv_plain_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
+                        at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
+                        int64_t, int64_t, int64_t, int64_t, int64_t);
+at::Tensor dia_spmv_dot_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
+                            at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             int64_t, int64_t, int64_t, int64_t, int64_t,
-                            int64_t);
-void dia_residual_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                      at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
-                      int64_t, int64_t, int64_t, int64_t, int64_t);
-void dia_jacobi_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                            int64_t, int64_t);
+void dia_residual_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
+                      at::Tensor, at::Tensor, at::Tensor, at::Tensor, int64_t,
+                      int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
+void dia_jacobi_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, int64_t, int64_t, int64_t, int64_t, int64_t,
                     double, int64_t, int64_t);
@@ -116,20 +121,27 @@ TORCH_LIBRARY(sparse_hip, m) {
         "int W, int m, int col_lo, float omega) -> ()");
   m.def("cg_xr_norm2(Tensor(a!) x, Tensor p, Tensor(b!) r, Tensor q, "
         "Tensor a, Tensor b, Tensor(c!) dot_out) -> ()");
-  m.def("dia_spmv_bpdot(Tensor dvals, Tensor offs, Tensor r_hlo, Tensor r_own, "
+  m.def("dia_classify(Tensor dvals, Tensor(a!) cvals, Tensor(b!) mask, "
+        "Tensor(c!) ok, int W) -> ()");
+  m.def("dia_spmv_bpdot(Tensor planes, Tensor? mask, Tensor offs, "
+        "Tensor r_hlo, Tensor r_own, "
         "Tensor r_hhi, Tensor p_hlo, Tensor p_own, Tensor p_hhi, "
         "Tensor(a!) pnew, Tensor(b!) q, Tensor beta_num, Tensor beta_den, "
         "int W, int m, int col_lo, int row0, int wsize) -> Tensor");
-  m.def("dia_spmv(Tensor dvals, Tensor offs, Tensor hlo, Tensor own, "
+  m.def("dia_spmv(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
+        "Tensor own, "
         "Tensor hhi, Tensor(a!) y, int W, int m, int col_lo, int row0, "
         "int wsize, int rbase, int rhi) -> ()");
-  m.def("dia_spmv_dot(Tensor dvals, Tensor offs, Tensor hlo, Tensor own, "
+  m.def("dia_spmv_dot(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
+        "Tensor own, "
         "Tensor hhi, Tensor(a!) y, Tensor pvec, int W, int m, int col_lo, "
         "int row0, int wsize, int rbase, int rhi) -> Tensor");
-  m.def("dia_residual(Tensor dvals, Tensor offs, Tensor hlo, Tensor own, "
+  m.def("dia_residual(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
+        "Tensor own, "
         "Tensor hhi, Tensor b, Tensor(a!) y, int W, int m, int col_lo, "
         "int row0, int wsize, int rbase, int rhi) -> ()");
-  m.def("dia_jacobi(Tensor dvals, Tensor offs, Tensor hlo, Tensor own, "
+  m.def("dia_jacobi(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
+        "Tensor own, "
         "Tensor hhi, Tensor xloc, Tensor b, Tensor dinv, Tensor(a!) xout, "
         "int W, int m, int col_lo, int row0, int wsize, float omega, "
         "int rbase, int rhi) -> ()");
@@ -181,6 +193,7 @@ TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
   m.impl("ell_spmv_dot", ell_spmv_dot_hip);
   m.impl("ell_jacobi", ell_jacobi_hip);
   m.impl("cg_xr_norm2", cg_xr_norm2_hip);
+  m.impl("dia_classify", dia_classify_hip);
   m.impl("dia_spmv_bpdot", dia_spmv_bpdot_hip);
   m.impl("dia_spmv", dia_spmv_plain_hip);
   m.impl("dia_spmv_dot", dia_spmv_dot_hip);

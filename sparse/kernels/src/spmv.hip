@@ -20,7 +20,9 @@
 // Below it: the padded-ELL and device-DIA mirrors and their row-pair kernel
 // family (ell_spmv, ell_jacobi, dia_spmv incl. the residual, dia_jacobi,
 // dia_spmv_bpdot), which share one window view, one accumulate loop per
-// format, one block reduction and one host launch helper.
+// format, one block reduction and one host launch helper.  The DIA loop
+// takes its plane values from a provider: the streamed planes, or plane
+// constants plus a row mask for constant-coefficient stencils.
 #include <type_traits>
 
 #include "common.h"
@@ -333,6 +335,50 @@ __global__ void build_dia_kernel(const int64_t* __restrict__ indptr,
   }
 }
 
+// Exact classification of the filled planes for DiaConstPlanes (below), on
+// BIT PATTERNS: -0.0 is not +0.0 and a NaN constant is just a pattern.
+//
+// Pass 1: cbits[k] = the bits of some entry of plane k that are not +0.0
+// (cbits pre-zeroed; a plane without one keeps 0).  blockIdx.y is the
+// plane, the x grid strides over its rows.  The plain store races
+// benignly: any winner will do, pass 2 is the check.
+template <typename B>
+__global__ void dia_plane_const_kernel(const B* __restrict__ dbits,
+                                       B* __restrict__ cbits, int64_t mp) {
+  const B* plane = dbits + (int64_t)blockIdx.y * mp;
+  B seen = 0;
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < mp;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const B b = plane[r];
+    if (b != 0) seen = b;
+  }
+  if (seen != 0 && cbits[blockIdx.y] != seen) cbits[blockIdx.y] = seen;
+}
+
+// Pass 2, one thread per padded row: pack bit k = (entry k of the row is
+// not +0.0) into the row's mask word, and clear *ok when such an entry
+// differs from cbits[k].
+template <typename B, typename M>
+__global__ void dia_row_mask_kernel(const B* __restrict__ dbits,
+                                    const B* __restrict__ cbits,
+                                    M* __restrict__ mask,
+                                    int32_t* __restrict__ ok, int64_t mp,
+                                    int W) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= mp) return;
+  uint32_t word = 0;
+  bool same = true;
+  for (int k = 0; k < W; ++k) {
+    const B b = dbits[(int64_t)k * mp + r];
+    if (b != 0) {
+      word |= 1u << k;
+      same = same && b == cbits[k];
+    }
+  }
+  mask[r] = (M)word;
+  if (!same && *ok != 0) *ok = 0;
+}
+
 
 // ---------------------------------------------------------------------------
 // Row-pair core shared by the ELL and DIA kernels below.  Every thread owns
@@ -362,6 +408,13 @@ struct XWindow {
     return hhi[idx - nown];
   }
 
+  // address of window-relative index idx, chosen by selects
+  __device__ __forceinline__ const T* flat_ptr(int64_t idx) const {
+    const bool lo = idx < nlo, mid = idx < nlo + nown;
+    const T* base = lo ? hlo : (mid ? own : hhi);
+    return base + (idx - (lo ? 0 : (mid ? nlo : nlo + nown)));
+  }
+
   // adjacent pair [c0, c0+1], clamped at the window edges (DIA: padded
   // plane entries are 0, so a clamped load is safe).  Rows r0, r0+1 of one
   // thread access consecutive columns on every diagonal, and the alignment
@@ -369,8 +422,25 @@ struct XWindow {
   // interior fast path is one 16B load (even parity) or two scalars (odd) —
   // halving the load-issue count that bounds the DIA kernels (profiled
   // 4.6 TB/s issue-bound vs 6.0 achievable).
-  template <bool SINGLE>
+  //
+  // FLAT: the same two elements through clamped addresses and selects, no
+  // branch — for callers that batch the pairs of several diagonals (a
+  // branchy pair makes the compiler drain the earlier loads before it
+  // forms the next addresses).
+  template <bool SINGLE, bool FLAT = false>
   __device__ __forceinline__ void pair(int64_t c0, T& x0, T& x1) const {
+    if (FLAT) {
+      const int64_t i0 = min(max(c0, (int64_t)0), wsize - 1);
+      const int64_t i1 = min(max(c0 + 1, (int64_t)0), wsize - 1);
+      if (SINGLE) {
+        x0 = own[i0];
+        x1 = own[i1];
+      } else {
+        x0 = *flat_ptr(i0);
+        x1 = *flat_ptr(i1);
+      }
+      return;
+    }
     if (SINGLE) {
       if (c0 >= 0 && c0 + 1 < wsize) {
         if ((c0 & 1) == 0) {
@@ -411,22 +481,107 @@ __device__ __forceinline__ void ell_accumulate(
   }
 }
 
-// a0, a1 += sum_k dvals[k][r0, r0+1] * xpair(cbase + offs[k]); cbase is the
+// Plane-value providers of the DIA core: rows(r0) is the thread's view of
+// rows r0, r0+1 (r0 even) and rows(r0).at(k, v0, v1) yields their entries
+// on plane k.
+//
+// DiaPlanes streams the (W, mp) column-major padded planes.
+template <typename T>
+struct DiaPlanes {
+  static constexpr int kBatch = 1;  // diagonals per load batch (accumulate)
+  const T* __restrict__ dvals;
+  int64_t mp;
+
+  struct Rows {
+    const T* __restrict__ p;
+    int64_t mp;
+    __device__ __forceinline__ void at(int k, T& v0, T& v1) const {
+      const int64_t base = (int64_t)k * mp;
+      v0 = nt_load(&p[base]);
+      v1 = nt_load(&p[base + 1]);
+    }
+  };
+  __device__ __forceinline__ Rows rows(int64_t r0) const {
+    return {dvals + r0, mp};
+  }
+};
+
+// DiaConstPlanes serves a mirror whose every plane k holds, bit for bit,
+// only +0.0 and one constant c[k] (constant-coefficient stencils): the W
+// constants plus one row-major mask word per row (bit k = plane k has c[k]
+// in this row; padded rows 0) replace the W values per row.  A thread
+// fetches both rows' words in one naturally aligned load (a wave reads one
+// contiguous 128 * sizeof(M) bytes) and c[k] is wave-uniform like offs[k].
+// A masked-out entry yields the same +0.0 the plane would hold, so the
+// accumulation — x loads included — is the streamed one and the results
+// are bit-identical to DiaPlanes.
+template <int BYTES> struct UIntOf;
+template <> struct UIntOf<2> { using type = uint16_t; };
+template <> struct UIntOf<4> { using type = uint32_t; };
+template <> struct UIntOf<8> { using type = uint64_t; };
+
+template <typename T, typename M>
+struct DiaConstPlanes {
+  static constexpr int kBatch = 8;
+  const T* __restrict__ cvals;  // W plane constants
+  const M* __restrict__ mask;   // mp row mask words
+
+  struct Rows {
+    const T* __restrict__ c;
+    uint32_t m0, m1;
+    __device__ __forceinline__ void at(int k, T& v0, T& v1) const {
+      const T ck = c[k];
+      const uint32_t bit = 1u << k;
+      v0 = (m0 & bit) ? ck : T(0);
+      v1 = (m1 & bit) ? ck : T(0);
+    }
+  };
+  __device__ __forceinline__ Rows rows(int64_t r0) const {
+    using M2 = typename UIntOf<2 * sizeof(M)>::type;
+    const M2 w = nt_load(reinterpret_cast<const M2*>(&mask[r0]));
+    return {cvals, (uint32_t)(M)w, (uint32_t)(w >> (8 * sizeof(M)))};
+  }
+};
+
+// a0, a1 += sum_k plane[k][r0, r0+1] * xpair(cbase + offs[k]); cbase is the
 // window-relative column of row r0 on the main diagonal and xpair(c0, x0,
 // x1) yields the x pair at window columns c0, c0+1.
-template <typename T, typename XPair>
+template <typename T, typename Planes, typename XPair>
 __device__ __forceinline__ void dia_accumulate(
-    const T* __restrict__ dvals, const int64_t* __restrict__ offs, int W,
-    int64_t mp, int64_t r0, int64_t cbase, XPair xpair, T& a0, T& a1) {
-  for (int k = 0; k < W; ++k) {
-    const int64_t base = (int64_t)k * mp + r0;
-    Pair<T> vv;
-    vv.a = nt_load(&dvals[base]);
-    vv.b = nt_load(&dvals[base + 1]);
-    T x0, x1;
-    xpair(cbase + offs[k], x0, x1);
-    a0 += vv.a * x0;
-    a1 += vv.b * x1;
+    const Planes& planes, const int64_t* __restrict__ offs, int W, int64_t r0,
+    int64_t cbase, XPair xpair, T& a0, T& a1) {
+  const auto rows = planes.rows(r0);
+  constexpr int U = Planes::kBatch;
+  if constexpr (U == 1) {
+    for (int k = 0; k < W; ++k) {
+      T v0, v1;
+      rows.at(k, v0, v1);
+      T x0, x1;
+      xpair(cbase + offs[k], x0, x1);
+      a0 += v0 * x0;
+      a1 += v1 * x1;
+    }
+  } else {
+    // fetch the x pairs of up to U diagonals before the first use, then
+    // accumulate in the same k order (same arithmetic, same bits): without
+    // a plane stream a thread has only its x loads to keep in flight, and
+    // one diagonal per round trip leaves the kernel latency-bound
+    for (int k = 0; k < W; k += U) {
+      T x0[U], x1[U];
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        if (k + j < W) xpair(cbase + offs[k + j], x0[j], x1[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < U; ++j) {
+        if (k + j < W) {
+          T v0, v1;
+          rows.at(k + j, v0, v1);
+          a0 += v0 * x0[j];
+          a1 += v1 * x1[j];
+        }
+      }
+    }
   }
 }
 
@@ -518,12 +673,19 @@ __global__ __launch_bounds__(BLK) void ell_jacobi_kernel(
 // (col - row values), store ONLY the padded value planes column-major plus
 // the W offsets — the index stream disappears (12 -> 8 B/nnz for
 // fp64+int32).  Invalid/padded entries hold 0 and their x loads are clamped
-// into the window.  Reference context: the dia format (sparse/dia.py) is a
+// into the window.  When every plane is one constant wherever it is not
+// +0.0 (constant-coefficient stencils: Poisson, banded, the GMG fine
+// levels) the planes themselves disappear too: the kernels take their
+// values from W constants and one mask word per row (DiaConstPlanes;
+// classified exactly at mirror build, dia_classify) — 1-4 B/row instead of
+// W values, same bits out.  Every kernel below is instantiated for both
+// value sources.  Reference context: the dia format (sparse/dia.py) is a
 // host/conversion format there; here it is the SpMV execution format for
 // banded operators (Poisson, dot_microbenchmark).
-template <typename T, bool FUSE_DOT, bool SINGLE, bool RESID = false>
+template <typename T, typename Planes, bool FUSE_DOT, bool SINGLE,
+          bool RESID = false>
 __global__ __launch_bounds__(BLK) void dia_spmv_kernel(
-    const T* __restrict__ dvals,  // (W, mp) column-major planes
+    const Planes planes,               // plane values (provider, above)
     const int64_t* __restrict__ offs,  // W diagonal offsets
     const XWindow<T> win, T* __restrict__ y, const T* __restrict__ pvec,
     T* __restrict__ dot_partial, int64_t m, int64_t mp, int W, int64_t col_lo,
@@ -533,9 +695,9 @@ __global__ __launch_bounds__(BLK) void dia_spmv_kernel(
   T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
   if (r0 < rhi) {
     dia_accumulate(
-        dvals, offs, W, mp, r0, row0 + r0 - col_lo,
+        planes, offs, W, r0, row0 + r0 - col_lo,
         [&](int64_t c0, T& x0, T& x1) {
-          win.template pair<SINGLE>(c0, x0, x1);
+          win.template pair<SINGLE, Planes::kBatch != 1>(c0, x0, x1);
         },
         a0, a1);
     if (!RESID) {
@@ -557,9 +719,9 @@ __global__ __launch_bounds__(BLK) void dia_spmv_kernel(
   }
 }
 
-template <typename T, bool SINGLE>
+template <typename T, typename Planes, bool SINGLE>
 __global__ __launch_bounds__(BLK) void dia_jacobi_kernel(
-    const T* __restrict__ dvals, const int64_t* __restrict__ offs,
+    const Planes planes, const int64_t* __restrict__ offs,
     const XWindow<T> win, const T* __restrict__ xloc,
     const T* __restrict__ b, const T* __restrict__ dinv,
     T* __restrict__ xout, int64_t m, int64_t mp, int W, int64_t col_lo,
@@ -568,8 +730,10 @@ __global__ __launch_bounds__(BLK) void dia_jacobi_kernel(
   if (r0 >= rhi) return;
   T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
   dia_accumulate(
-      dvals, offs, W, mp, r0, row0 + r0 - col_lo,
-      [&](int64_t c0, T& x0, T& x1) { win.template pair<SINGLE>(c0, x0, x1); },
+      planes, offs, W, r0, row0 + r0 - col_lo,
+      [&](int64_t c0, T& x0, T& x1) {
+        win.template pair<SINGLE, Planes::kBatch != 1>(c0, x0, x1);
+      },
       a0, a1);
   jacobi_update(xloc, b, dinv, xout, omega, r0, m, rhi, a0, a1);
 }
@@ -584,9 +748,9 @@ __global__ __launch_bounds__(BLK) void dia_jacobi_kernel(
 // p_new MUST be distinct buffers (double-buffered by the caller).
 // Reference context: this is the MI355X fusion of the reference CG loop's
 // AXPBY + SpMV + dot task chain (linalg.py:499-565).
-template <typename T, bool SINGLE>
+template <typename T, typename Planes, bool SINGLE>
 __global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
-    const T* __restrict__ dvals, const int64_t* __restrict__ offs,
+    const Planes planes, const int64_t* __restrict__ offs,
     const XWindow<T> rwin, const XWindow<T> pwin, T* __restrict__ pnew,
     T* __restrict__ q, const T* __restrict__ beta_num,
     const T* __restrict__ beta_den, T* __restrict__ dot_partial, int64_t m,
@@ -599,14 +763,14 @@ __global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
   if (r0 < mp) {
     auto pnew_pair = [&](int64_t c0, T& x0, T& x1) {
       T r0v, r1v, p0v, p1v;
-      rwin.template pair<SINGLE>(c0, r0v, r1v);
-      pwin.template pair<SINGLE>(c0, p0v, p1v);
+      rwin.template pair<SINGLE, Planes::kBatch != 1>(c0, r0v, r1v);
+      pwin.template pair<SINGLE, Planes::kBatch != 1>(c0, p0v, p1v);
       x0 = r0v + beta * p0v;
       x1 = r1v + beta * p1v;
     };
     // window index of own row r0: row0 - col_lo + r0
     const int64_t cbase = row0 + r0 - col_lo;
-    dia_accumulate(dvals, offs, W, mp, r0, cbase, pnew_pair, a0, a1);
+    dia_accumulate(planes, offs, W, r0, cbase, pnew_pair, a0, a1);
     // own-row p_new (same formula as the window recompute => identical fp);
     // p1 of a lone tail row is a clamped load that is never used
     pnew_pair(cbase, p0, p1);
@@ -635,10 +799,10 @@ struct RowPairLaunch {
   int64_t mp, rbase, rhi, nlo, nown, wsize, nblocks;
   bool single;  // no halo pieces: the own slab is the whole window
 
-  RowPairLaunch(const at::Tensor& planes, int64_t W, const at::Tensor& hlo,
-                const at::Tensor& own, const at::Tensor& hhi, int64_t wsize_,
-                int64_t rbase_ = 0, int64_t rhi_ = -1)
-      : mp(planes.numel() / W), rbase(rbase_), rhi(rhi_ < 0 ? mp : rhi_),
+  RowPairLaunch(int64_t mp_, const at::Tensor& hlo, const at::Tensor& own,
+                const at::Tensor& hhi, int64_t wsize_, int64_t rbase_ = 0,
+                int64_t rhi_ = -1)
+      : mp(mp_), rbase(rbase_), rhi(rhi_ < 0 ? mp : rhi_),
         nlo(hlo.numel()), nown(own.numel()), wsize(wsize_),
         nblocks(rhi > rbase ? pair_blocks(rhi - rbase) : 0),
         single(nlo == 0 && hhi.numel() == 0) {}
@@ -661,6 +825,49 @@ struct RowPairLaunch {
                        static_cast<P>(args)...);
   }
 };
+
+// A DIA op's value source is (planes, mask): without a mask `planes` holds
+// the (W, mp) streamed planes; with one it holds the W plane constants and
+// `mask` the mp row words (DiaConstPlanes; real types, W <= 32).
+using OptTensor = c10::optional<at::Tensor>;
+
+inline int64_t dia_mp(const at::Tensor& planes, const OptTensor& mask,
+                      int64_t W) {
+  return mask ? mask->numel() : planes.numel() / W;
+}
+
+// f(provider) for the value source of a DIA op
+template <typename T, typename F>
+void dispatch_dia_planes(const at::Tensor& planes, const OptTensor& mask,
+                         int64_t W, F&& f) {
+  if (!mask) {
+    f(DiaPlanes<T>{planes.data_ptr<T>(), planes.numel() / W});
+    return;
+  }
+  if constexpr (std::is_floating_point_v<T>) {
+    TORCH_CHECK(planes.numel() == W && W <= 8 * (int64_t)mask->element_size() &&
+                    mask->numel() % 2 == 0,
+                "dia: W constants and an even number of mask words of at "
+                "least W bits expected");
+    const T* c = planes.data_ptr<T>();
+    const void* mw = mask->data_ptr();
+    switch (mask->scalar_type()) {
+      case at::kByte:
+        f(DiaConstPlanes<T, uint8_t>{c, static_cast<const uint8_t*>(mw)});
+        return;
+      case at::kUInt16:
+        f(DiaConstPlanes<T, uint16_t>{c, static_cast<const uint16_t*>(mw)});
+        return;
+      case at::kUInt32:
+        f(DiaConstPlanes<T, uint32_t>{c, static_cast<const uint32_t*>(mw)});
+        return;
+      default:
+        break;
+    }
+  }
+  TORCH_CHECK(false, "dia: constant planes need a real value type and a "
+                     "uint8/uint16/uint32 row mask");
+}
 
 }  // namespace
 
@@ -700,6 +907,49 @@ void build_dia_hip(at::Tensor indptr, at::Tensor indices, at::Tensor values,
   });
 }
 
+// Classify the filled planes (fp32/fp64) for the constant-plane source:
+// cvals (W, pre-zeroed) receives the plane constants, mask (mp words) the
+// row masks, and ok[0] (preset to 1) is cleared unless every plane holds
+// only +0.0 and its constant.  One extra read of the planes at mirror
+// build; nothing here runs per SpMV.
+void dia_classify_hip(at::Tensor dvals, at::Tensor cvals, at::Tensor mask,
+                      at::Tensor ok, int64_t W) {
+  const int64_t mp = mask.numel();
+  TORCH_CHECK(dvals.numel() == W * mp && cvals.numel() == W &&
+                  cvals.scalar_type() == dvals.scalar_type() &&
+                  ok.scalar_type() == at::kInt &&
+                  W <= 8 * (int64_t)mask.element_size(),
+              "dia_classify: inconsistent arguments");
+  if (mp == 0) return;
+  const dim3 g1((unsigned)std::min<int64_t>((mp + 255) / 256, 1024),
+                (unsigned)W);
+  auto run = [&](auto bits, auto word) {
+    using B = decltype(bits);
+    using M = decltype(word);
+    const B* d = static_cast<const B*>(dvals.data_ptr());
+    B* c = static_cast<B*>(cvals.data_ptr());
+    hipLaunchKernelGGL((dia_plane_const_kernel<B>), g1, dim3(256), 0,
+                       cur_stream(), d, c, mp);
+    hipLaunchKernelGGL((dia_row_mask_kernel<B, M>), dim3((mp + 255) / 256),
+                       dim3(256), 0, cur_stream(), d, c,
+                       static_cast<M*>(mask.data_ptr()),
+                       ok.data_ptr<int32_t>(), mp, (int)W);
+  };
+  auto by_word = [&](auto bits) {
+    switch (mask.scalar_type()) {
+      case at::kByte: run(bits, uint8_t{}); break;
+      case at::kUInt16: run(bits, uint16_t{}); break;
+      case at::kUInt32: run(bits, uint32_t{}); break;
+      default: TORCH_CHECK(false, "dia_classify: mask must be uint8/16/32");
+    }
+  };
+  switch (dvals.scalar_type()) {
+    case at::kFloat: by_word(uint32_t{}); break;
+    case at::kDouble: by_word(uint64_t{}); break;
+    default: TORCH_CHECK(false, "dia_classify: fp32/fp64 planes only");
+  }
+}
+
 // The fused-dot ops own their per-block partials: one slot per launched
 // block, every block writes its slot, and the 0-dim sum is returned (an
 // empty row range is an exact zero).
@@ -714,7 +964,7 @@ static at::Tensor ell_spmv_impl(const at::Tensor& eidx, const at::Tensor& evals,
                                 const at::Tensor& hhi, at::Tensor& y,
                                 const at::Tensor* pvec, int64_t W, int64_t m,
                                 int64_t col_lo, int64_t rbase, int64_t rhi) {
-  const RowPairLaunch L(evals, W, hlo, own, hhi, 0, rbase, rhi);
+  const RowPairLaunch L(evals.numel() / W, hlo, own, hhi, 0, rbase, rhi);
   at::Tensor partial;
   if (L.empty()) return partial;
   if (pvec) partial = at::empty({L.nblocks}, evals.options());
@@ -758,7 +1008,7 @@ void ell_jacobi_hip(at::Tensor eidx, at::Tensor evals, at::Tensor hlo,
                     at::Tensor own, at::Tensor hhi, at::Tensor xloc,
                     at::Tensor b, at::Tensor dinv, at::Tensor xout,
                     int64_t W, int64_t m, int64_t col_lo, double omega) {
-  const RowPairLaunch L(evals, W, hlo, own, hhi, 0);
+  const RowPairLaunch L(evals.numel() / W, hlo, own, hhi, 0);
   if (L.empty()) return;
   DISPATCH_VALUES(evals.scalar_type(), "ell_jacobi", [&] {
     using T = scalar_t;
@@ -777,107 +1027,117 @@ void ell_jacobi_hip(at::Tensor eidx, at::Tensor evals, at::Tensor hlo,
 // y = A x on rows [rbase, rhi); with pvec also the partials of pvec . y;
 // RESID: y = b - A x, the fused V-cycle residual (the pvec slot carries b)
 template <bool RESID>
-static at::Tensor dia_spmv_impl(const at::Tensor& dvals, const at::Tensor& offs,
-                                const at::Tensor& hlo, const at::Tensor& own,
-                                const at::Tensor& hhi, at::Tensor& y,
-                                const at::Tensor* pvec, int64_t W, int64_t m,
-                                int64_t col_lo, int64_t row0, int64_t wsize,
-                                int64_t rbase, int64_t rhi) {
-  const RowPairLaunch L(dvals, W, hlo, own, hhi, wsize, rbase, rhi);
+static at::Tensor dia_spmv_impl(const at::Tensor& planes, const OptTensor& mask,
+                                const at::Tensor& offs, const at::Tensor& hlo,
+                                const at::Tensor& own, const at::Tensor& hhi,
+                                at::Tensor& y, const at::Tensor* pvec,
+                                int64_t W, int64_t m, int64_t col_lo,
+                                int64_t row0, int64_t wsize, int64_t rbase,
+                                int64_t rhi) {
+  const RowPairLaunch L(dia_mp(planes, mask, W), hlo, own, hhi, wsize, rbase,
+                        rhi);
   const bool fuse_dot = pvec && !RESID;
   at::Tensor partial;
   if (L.empty()) return partial;
-  if (fuse_dot) partial = at::empty({L.nblocks}, dvals.options());
-  DISPATCH_VALUES(dvals.scalar_type(), "dia_spmv", [&] {
+  if (fuse_dot) partial = at::empty({L.nblocks}, planes.options());
+  DISPATCH_VALUES(planes.scalar_type(), "dia_spmv", [&] {
     using T = scalar_t;
-    dispatch_bool(fuse_dot, [&](auto fuse) {
-      dispatch_bool(L.single, [&](auto single) {
-        if constexpr (!(RESID && decltype(fuse)::value)) {
-          L.launch(dia_spmv_kernel<T, decltype(fuse)::value,
-                                   decltype(single)::value, RESID>,
-                   dvals.data_ptr<T>(), offs.data_ptr<int64_t>(),
-                   L.window<T>(hlo, own, hhi), y.data_ptr<T>(),
-                   pvec ? pvec->data_ptr<T>() : nullptr,
-                   fuse_dot ? partial.data_ptr<T>() : nullptr, m, L.mp, W,
-                   col_lo, row0, L.rbase, L.rhi);
-        }
+    dispatch_dia_planes<T>(planes, mask, W, [&](auto pl) {
+      dispatch_bool(fuse_dot, [&](auto fuse) {
+        dispatch_bool(L.single, [&](auto single) {
+          if constexpr (!(RESID && decltype(fuse)::value)) {
+            L.launch(dia_spmv_kernel<T, decltype(pl), decltype(fuse)::value,
+                                     decltype(single)::value, RESID>,
+                     pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
+                     y.data_ptr<T>(), pvec ? pvec->data_ptr<T>() : nullptr,
+                     fuse_dot ? partial.data_ptr<T>() : nullptr, m, L.mp, W,
+                     col_lo, row0, L.rbase, L.rhi);
+          }
+        });
       });
     });
   });
   return partial;
 }
 
-void dia_spmv_plain_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
-                        at::Tensor own, at::Tensor hhi, at::Tensor y,
-                        int64_t W, int64_t m, int64_t col_lo, int64_t row0,
-                        int64_t wsize, int64_t rbase, int64_t rhi) {
-  dia_spmv_impl<false>(dvals, offs, hlo, own, hhi, y, nullptr, W, m, col_lo,
-                       row0, wsize, rbase, rhi);
+void dia_spmv_plain_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
+                        at::Tensor hlo, at::Tensor own, at::Tensor hhi,
+                        at::Tensor y, int64_t W, int64_t m, int64_t col_lo,
+                        int64_t row0, int64_t wsize, int64_t rbase,
+                        int64_t rhi) {
+  dia_spmv_impl<false>(planes, mask, offs, hlo, own, hhi, y, nullptr, W, m,
+                       col_lo, row0, wsize, rbase, rhi);
 }
 
-at::Tensor dia_spmv_dot_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
-                            at::Tensor own, at::Tensor hhi, at::Tensor y,
-                            at::Tensor pvec, int64_t W, int64_t m,
-                            int64_t col_lo, int64_t row0, int64_t wsize,
-                            int64_t rbase, int64_t rhi) {
-  return sum_or_zero(dia_spmv_impl<false>(dvals, offs, hlo, own, hhi, y, &pvec,
-                                          W, m, col_lo, row0, wsize, rbase,
-                                          rhi),
-                     dvals);
+at::Tensor dia_spmv_dot_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
+                            at::Tensor hlo, at::Tensor own, at::Tensor hhi,
+                            at::Tensor y, at::Tensor pvec, int64_t W,
+                            int64_t m, int64_t col_lo, int64_t row0,
+                            int64_t wsize, int64_t rbase, int64_t rhi) {
+  return sum_or_zero(dia_spmv_impl<false>(planes, mask, offs, hlo, own, hhi, y,
+                                          &pvec, W, m, col_lo, row0, wsize,
+                                          rbase, rhi),
+                     planes);
 }
 
-void dia_residual_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
-                      at::Tensor own, at::Tensor hhi, at::Tensor b,
-                      at::Tensor y, int64_t W, int64_t m, int64_t col_lo,
-                      int64_t row0, int64_t wsize, int64_t rbase,
-                      int64_t rhi) {
-  dia_spmv_impl<true>(dvals, offs, hlo, own, hhi, y, &b, W, m, col_lo, row0,
-                      wsize, rbase, rhi);
+void dia_residual_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
+                      at::Tensor hlo, at::Tensor own, at::Tensor hhi,
+                      at::Tensor b, at::Tensor y, int64_t W, int64_t m,
+                      int64_t col_lo, int64_t row0, int64_t wsize,
+                      int64_t rbase, int64_t rhi) {
+  dia_spmv_impl<true>(planes, mask, offs, hlo, own, hhi, y, &b, W, m, col_lo,
+                      row0, wsize, rbase, rhi);
 }
 
-void dia_jacobi_hip(at::Tensor dvals, at::Tensor offs, at::Tensor hlo,
-                    at::Tensor own, at::Tensor hhi, at::Tensor xloc,
-                    at::Tensor b, at::Tensor dinv, at::Tensor xout,
-                    int64_t W, int64_t m, int64_t col_lo, int64_t row0,
-                    int64_t wsize, double omega, int64_t rbase, int64_t rhi) {
-  const RowPairLaunch L(dvals, W, hlo, own, hhi, wsize, rbase, rhi);
+void dia_jacobi_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
+                    at::Tensor hlo, at::Tensor own, at::Tensor hhi,
+                    at::Tensor xloc, at::Tensor b, at::Tensor dinv,
+                    at::Tensor xout, int64_t W, int64_t m, int64_t col_lo,
+                    int64_t row0, int64_t wsize, double omega, int64_t rbase,
+                    int64_t rhi) {
+  const RowPairLaunch L(dia_mp(planes, mask, W), hlo, own, hhi, wsize, rbase,
+                        rhi);
   if (L.empty()) return;
-  DISPATCH_VALUES(dvals.scalar_type(), "dia_jacobi", [&] {
+  DISPATCH_VALUES(planes.scalar_type(), "dia_jacobi", [&] {
     using T = scalar_t;
-    dispatch_bool(L.single, [&](auto single) {
-      L.launch(dia_jacobi_kernel<T, decltype(single)::value>,
-               dvals.data_ptr<T>(), offs.data_ptr<int64_t>(),
-               L.window<T>(hlo, own, hhi), xloc.data_ptr<T>(),
-               b.data_ptr<T>(), dinv.data_ptr<T>(), xout.data_ptr<T>(), m,
-               L.mp, W, col_lo, row0, omega, L.rbase, L.rhi);
+    dispatch_dia_planes<T>(planes, mask, W, [&](auto pl) {
+      dispatch_bool(L.single, [&](auto single) {
+        L.launch(dia_jacobi_kernel<T, decltype(pl), decltype(single)::value>,
+                 pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
+                 xloc.data_ptr<T>(), b.data_ptr<T>(), dinv.data_ptr<T>(),
+                 xout.data_ptr<T>(), m, L.mp, W, col_lo, row0, omega, L.rbase,
+                 L.rhi);
+      });
     });
   });
 }
 
-at::Tensor dia_spmv_bpdot_hip(at::Tensor dvals, at::Tensor offs,
-                              at::Tensor r_hlo, at::Tensor r_own,
-                              at::Tensor r_hhi, at::Tensor p_hlo,
-                              at::Tensor p_own, at::Tensor p_hhi,
-                              at::Tensor pnew, at::Tensor q,
+at::Tensor dia_spmv_bpdot_hip(at::Tensor planes, OptTensor mask,
+                              at::Tensor offs, at::Tensor r_hlo,
+                              at::Tensor r_own, at::Tensor r_hhi,
+                              at::Tensor p_hlo, at::Tensor p_own,
+                              at::Tensor p_hhi, at::Tensor pnew, at::Tensor q,
                               at::Tensor beta_num, at::Tensor beta_den,
                               int64_t W, int64_t m, int64_t col_lo,
                               int64_t row0, int64_t wsize) {
   TORCH_CHECK(pnew.data_ptr() != p_own.data_ptr(),
               "dia_spmv_bpdot: pnew must not alias p_own (double-buffer)");
-  const RowPairLaunch L(dvals, W, r_hlo, r_own, r_hhi, wsize);
+  const RowPairLaunch L(dia_mp(planes, mask, W), r_hlo, r_own, r_hhi, wsize);
   at::Tensor partial;
-  if (L.empty()) return sum_or_zero(partial, dvals);
-  partial = at::empty({L.nblocks}, dvals.options());
-  DISPATCH_VALUES(dvals.scalar_type(), "dia_spmv_bpdot", [&] {
+  if (L.empty()) return sum_or_zero(partial, planes);
+  partial = at::empty({L.nblocks}, planes.options());
+  DISPATCH_VALUES(planes.scalar_type(), "dia_spmv_bpdot", [&] {
     using T = scalar_t;
-    dispatch_bool(L.single, [&](auto single) {
-      L.launch(dia_spmv_bpdot_kernel<T, decltype(single)::value>,
-               dvals.data_ptr<T>(), offs.data_ptr<int64_t>(),
-               L.window<T>(r_hlo, r_own, r_hhi),
-               L.window<T>(p_hlo, p_own, p_hhi), pnew.data_ptr<T>(),
-               q.data_ptr<T>(), beta_num.data_ptr<T>(),
-               beta_den.data_ptr<T>(), partial.data_ptr<T>(), m, L.mp, W,
-               col_lo, row0);
+    dispatch_dia_planes<T>(planes, mask, W, [&](auto pl) {
+      dispatch_bool(L.single, [&](auto single) {
+        L.launch(dia_spmv_bpdot_kernel<T, decltype(pl), decltype(single)::value>,
+                 pl, offs.data_ptr<int64_t>(),
+                 L.window<T>(r_hlo, r_own, r_hhi),
+                 L.window<T>(p_hlo, p_own, p_hhi), pnew.data_ptr<T>(),
+                 q.data_ptr<T>(), beta_num.data_ptr<T>(),
+                 beta_den.data_ptr<T>(), partial.data_ptr<T>(), m, L.mp, W,
+                 col_lo, row0);
+      });
     });
   });
   return partial.sum();

@@ -259,11 +259,13 @@ def cg(A, b, x0=None, tol=1e-5, maxiter=None, M=None, callback=None, atol=None,
         # two-kernel CG iteration on the DIA fast path: K1 folds the
         # p-update into the SpMV (p = r + beta p, q = Ap, p.q), K2 fuses
         # x += alpha p, r -= alpha q and |r|^2.  MEASURED SLOWER than the
-        # 4-kernel loop on MI355X at nx=16384 (6.14 vs 5.89 ms/iter:
-        # K1 streams TWO vector windows through L2 and is issue-bound at
-        # 5.0 TB/s while the axpby passes it replaces run at 6.0), so this
-        # is opt-in via SPARSE_CG2=1; kept because the tradeoff may flip
-        # for wider stencils (more dvals reuse per vector byte).
+        # 3-kernel loop on MI355X at nx=16384: 4.86 vs 4.69 ms/iter with
+        # the compressed (constant-plane) DIA mirror, where K1 no longer
+        # streams value planes and its TWO vector windows through L2 are
+        # all it waits for (profiles/dia_constplane_bench.txt); about level
+        # (5.93 vs 6.04) with streamed planes.  So this stays opt-in via
+        # SPARSE_CG2=1; kept because the tradeoff may flip for wider
+        # non-constant stencils (more plane bytes per vector byte).
         from . import kernels
 
         p_b = darray.zeros((n,), dtype=A.dtype)
