@@ -88,6 +88,45 @@ __device__ __forceinline__ int64_t xcd_swizzle(int64_t bid, int64_t nwg) {
   return (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + idx;
 }
 
+// Sum over the 64 lanes of a wave by cross-lane shuffles; lane 0 holds the
+// result.  Fixed order, so the sum is reproducible from run to run.
+template <typename T>
+__device__ __forceinline__ T wave_reduce_sum(T v) {
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, WAVE);
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ c10::complex<T> wave_reduce_sum(c10::complex<T> v) {
+  return {wave_reduce_sum(v.real()), wave_reduce_sum(v.imag())};
+}
+
+// N independent sums over a 256-thread block with ONE barrier: a wave
+// reduction by shuffles, then the four wave sums through LDS.  Thread t < N
+// returns sum t (v[t] over the block), the other threads return zero.  Every
+// thread of the block must call it, at most once per kernel (the LDS slots
+// are not guarded against a second use).  The LDS tree it replaces took nine
+// barriers (profiles/dia_core_chain_profile.md).
+template <int N = 1, typename T>
+__device__ __forceinline__ T block_sums_256(const T (&v)[N]) {
+  constexpr int NW = 256 / WAVE;
+  __shared__ __align__(16) char raw[N * NW * sizeof(T)];
+  T* ws = reinterpret_cast<T*>(raw);
+  const int lane = threadIdx.x % WAVE, wid = threadIdx.x / WAVE;
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    const T s = wave_reduce_sum(v[n]);
+    if (lane == 0) ws[n * NW + wid] = s;
+  }
+  __syncthreads();
+  T s = ZeroOf<T>::value();
+  if (threadIdx.x < N) {
+    const T* w = ws + threadIdx.x * NW;
+    s = ((w[0] + w[1]) + w[2]) + w[3];
+  }
+  return s;
+}
+
 inline hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
 }

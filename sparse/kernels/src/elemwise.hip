@@ -266,7 +266,6 @@ __global__ __launch_bounds__(256) void axpby_norm2_kernel(
     const T* __restrict__ b, T* __restrict__ dot_partial, int64_t n) {
   // flat 16B-per-thread + per-block partial (wrapper sums; no atomics)
   constexpr int EPT = EptOf<T>::value;
-  __shared__ T red[256];
   T s = (*a) / (*b);
   if (NEG) s = -s;
   T acc = T(0);
@@ -291,13 +290,9 @@ __global__ __launch_bounds__(256) void axpby_norm2_kernel(
       acc += v * v;
     }
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) dot_partial[blockIdx.x] = red[0];
+  const T part[1] = {acc};
+  const T sum = block_sums_256(part);
+  if (threadIdx.x == 0) dot_partial[blockIdx.x] = sum;
 }
 
 // CG K2: x += (a/b) p ; r -= (a/b) q ; per-block partials of sum(r_new^2).
@@ -310,7 +305,6 @@ __global__ __launch_bounds__(256) void cg_xr_norm2_kernel(
     const T* __restrict__ q, const T* __restrict__ a, const T* __restrict__ b,
     T* __restrict__ dot_partial, int64_t n) {
   constexpr int EPT = EptOf<T>::value;
-  __shared__ T red[256];
   const T s = (*a) / (*b);
   T acc = T(0);
   const int64_t nv = n / EPT;
@@ -341,13 +335,9 @@ __global__ __launch_bounds__(256) void cg_xr_norm2_kernel(
       acc += rv * rv;
     }
   }
-  red[threadIdx.x] = acc;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) dot_partial[blockIdx.x] = red[0];
+  const T part[1] = {acc};
+  const T sum = block_sums_256(part);
+  if (threadIdx.x == 0) dot_partial[blockIdx.x] = sum;
 }
 
 }  // namespace

@@ -543,6 +543,22 @@ struct DiaConstPlanes {
   }
 };
 
+// a + v * x.  Real types: in ONE rounding, spelled out in every DIA kernel
+// — contraction would make the same of `a += v * x`, but left to the
+// compiler the vectorizer may instead split an fp32 row pair into a packed
+// multiply and an add in one instantiation and not in another, and the DIA
+// kernels promise the same bits from both value sources.
+template <typename T>
+__device__ __forceinline__ T fmadd(T v, T x, T a) {
+  if constexpr (std::is_same_v<T, float>) {
+    return __builtin_fmaf(v, x, a);
+  } else if constexpr (std::is_same_v<T, double>) {
+    return __builtin_fma(v, x, a);
+  } else {
+    return a + v * x;
+  }
+}
+
 // a0, a1 += sum_k plane[k][r0, r0+1] * xpair(cbase + offs[k]); cbase is the
 // window-relative column of row r0 on the main diagonal and xpair(c0, x0,
 // x1) yields the x pair at window columns c0, c0+1.
@@ -558,8 +574,8 @@ __device__ __forceinline__ void dia_accumulate(
       rows.at(k, v0, v1);
       T x0, x1;
       xpair(cbase + offs[k], x0, x1);
-      a0 += v0 * x0;
-      a1 += v1 * x1;
+      a0 = fmadd(v0, x0, a0);
+      a1 = fmadd(v1, x1, a1);
     }
   } else {
     // fetch the x pairs of up to U diagonals before the first use, then
@@ -577,8 +593,8 @@ __device__ __forceinline__ void dia_accumulate(
         if (k + j < W) {
           T v0, v1;
           rows.at(k + j, v0, v1);
-          a0 += v0 * x0[j];
-          a1 += v1 * x1[j];
+          a0 = fmadd(v0, x0[j], a0);
+          a1 = fmadd(v1, x1[j], a1);
         }
       }
     }
@@ -608,21 +624,21 @@ __device__ __forceinline__ void jacobi_update(
     const Pair<T> bv = *reinterpret_cast<const Pair<T>*>(&b[r0]);
     const Pair<T> dv = *reinterpret_cast<const Pair<T>*>(&dinv[r0]);
     *reinterpret_cast<Pair<T>*>(&xout[r0]) =
-        Pair<T>{xv.a + omega * dv.a * (bv.a - a0),
-                xv.b + omega * dv.b * (bv.b - a1)};
+        Pair<T>{fmadd(omega * dv.a, bv.a - a0, xv.a),
+                fmadd(omega * dv.b, bv.b - a1, xv.b)};
   } else if (r0 < m) {
-    xout[r0] = xloc[r0] + omega * dinv[r0] * (b[r0] - a0);
+    xout[r0] = fmadd(omega * dinv[r0], b[r0] - a0, xloc[r0]);
   }
 }
 
 // fused-dot epilogue: every thread of the block contributes d; slot
-// blockIdx.x of dot_partial receives the block sum
+// blockIdx.x of dot_partial receives the block sum (one barrier, common.h)
 template <typename T>
-__device__ __forceinline__ void block_dot_partial(T* red, T d,
+__device__ __forceinline__ void block_dot_partial(T d,
                                                   T* __restrict__ dot_partial) {
-  red[threadIdx.x] = d;
-  block_reduce_sum(red, (int)threadIdx.x);
-  if (threadIdx.x == 0) dot_partial[blockIdx.x] = red[0];
+  const T part[1] = {d};
+  const T sum = block_sums_256(part);
+  if (threadIdx.x == 0) dot_partial[blockIdx.x] = sum;
 }
 
 // [rbase, rhi): row sub-range (rbase even) — the interior/boundary split
@@ -634,7 +650,6 @@ __global__ __launch_bounds__(BLK) void ell_spmv_kernel(
     const XWindow<T> win, T* __restrict__ y, const T* __restrict__ pvec,
     T* __restrict__ dot_partial, int64_t m, int64_t mp, int W, int64_t col_lo,
     int64_t rbase, int64_t rhi) {
-  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
   const int64_t r0 = rbase + 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
   T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
   if (r0 < rhi) {
@@ -646,7 +661,7 @@ __global__ __launch_bounds__(BLK) void ell_spmv_kernel(
     T d = ZeroOf<T>::value();
     if (r0 < min(m, rhi)) d += a0 * pvec[r0];
     if (r0 + 1 < min(m, rhi)) d += a1 * pvec[r0 + 1];
-    block_dot_partial(reinterpret_cast<T*>(red_raw), d, dot_partial);
+    block_dot_partial(d, dot_partial);
   }
 }
 
@@ -690,7 +705,6 @@ __global__ __launch_bounds__(BLK) void dia_spmv_kernel(
     const XWindow<T> win, T* __restrict__ y, const T* __restrict__ pvec,
     T* __restrict__ dot_partial, int64_t m, int64_t mp, int W, int64_t col_lo,
     int64_t row0, int64_t rbase, int64_t rhi) {
-  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
   const int64_t r0 = rbase + 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
   T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
   if (r0 < rhi) {
@@ -713,9 +727,9 @@ __global__ __launch_bounds__(BLK) void dia_spmv_kernel(
   }
   if (FUSE_DOT) {
     T d = ZeroOf<T>::value();
-    if (r0 < min(m, rhi)) d += a0 * pvec[r0];
-    if (r0 + 1 < min(m, rhi)) d += a1 * pvec[r0 + 1];
-    block_dot_partial(reinterpret_cast<T*>(red_raw), d, dot_partial);
+    if (r0 < min(m, rhi)) d = fmadd(a0, pvec[r0], d);
+    if (r0 + 1 < min(m, rhi)) d = fmadd(a1, pvec[r0 + 1], d);
+    block_dot_partial(d, dot_partial);
   }
 }
 
@@ -755,7 +769,6 @@ __global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
     T* __restrict__ q, const T* __restrict__ beta_num,
     const T* __restrict__ beta_den, T* __restrict__ dot_partial, int64_t m,
     int64_t mp, int W, int64_t col_lo, int64_t row0) {
-  __shared__ __align__(16) char red_raw[BLK * sizeof(T)];
   const T beta = (*beta_num) / (*beta_den);
   const int64_t r0 = 2 * ((int64_t)blockIdx.x * BLK + threadIdx.x);
   T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
@@ -765,8 +778,8 @@ __global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
       T r0v, r1v, p0v, p1v;
       rwin.template pair<SINGLE, Planes::kBatch != 1>(c0, r0v, r1v);
       pwin.template pair<SINGLE, Planes::kBatch != 1>(c0, p0v, p1v);
-      x0 = r0v + beta * p0v;
-      x1 = r1v + beta * p1v;
+      x0 = fmadd(beta, p0v, r0v);
+      x1 = fmadd(beta, p1v, r1v);
     };
     // window index of own row r0: row0 - col_lo + r0
     const int64_t cbase = row0 + r0 - col_lo;
@@ -778,9 +791,298 @@ __global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
     store_pair_or_tail(q, r0, m, m, a0, a1);
   }
   T d = ZeroOf<T>::value();
-  if (r0 < m) d += a0 * p0;
-  if (r0 + 1 < m) d += a1 * p1;
-  block_dot_partial(reinterpret_cast<T*>(red_raw), d, dot_partial);
+  if (r0 < m) d = fmadd(a0, p0, d);
+  if (r0 + 1 < m) d = fmadd(a1, p1, d);
+  block_dot_partial(d, dot_partial);
+}
+
+// ---------------------------------------------------------------------------
+// Constant-plane kernels.  Without a plane stream a wave moves ~2 KB per trip
+// through its dependent chain (mask -> x -> operands -> reduction), so these
+// kernels are bound by latency per wave, not by HBM
+// (profiles/dia_core_chain_profile.md).  dia_const_rows shortens the chain:
+//  - a thread owns R row pairs, block-strided (pair j of thread t is rows
+//    rb + 2 * (t + j * BLK), so every wave instruction still touches one
+//    contiguous run) and issues the loads of all of them — mask words, the x
+//    pairs of every diagonal, the caller's operands — before the first use;
+//  - offs[] and c[] are fetched up front into registers; W <= 8 (the u8
+//    mask) is a compile-time WC so the diagonal loop unrolls fully and no
+//    scalar wait sits between the x loads;
+//  - a block whose rows are all below min(m, rhi) and whose columns all lie
+//    in the own piece of the window (block-uniform test, scalar branch) uses
+//    plain addresses: one 16-byte load per x pair where the pair is aligned
+//    (uniform per diagonal, see XWindow::pair), two 8-byte loads otherwise.
+//    The other (edge) blocks run the clamped dia_accumulate above.
+// Per-row arithmetic is dia_accumulate's (a += v_k * x_k, k ascending): same
+// bits as the streamed planes.  The fused dot keeps ONE partial per 2 * BLK
+// rows, i.e. R per block, summed exactly like a block of the streamed
+// kernel: both value sources return the same dot bits.
+constexpr int kDiaPairs = 2;       // R of dia_spmv / residual / jacobi
+constexpr int kDiaBpdotPairs = 1;  // R of dia_spmv_bpdot (two windows)
+
+// offs must be ascending (build_dia: torch.unique).  win0 and (NWIN == 2)
+// win1 share one geometry; comb(v) folds the NWIN loaded values of a column into its x.
+// pre(j, r0, full) issues the caller's operand loads of pair j and
+// post(j, r0, a0, a1, full) consumes its sums; full = rows r0, r0+1 are both
+// below min(m, rhi).  Edge blocks skip pairs with r0 >= rhi.
+template <int WC, int R, bool SINGLE, int NWIN, typename T, typename M,
+          typename Comb, typename Pre, typename Post>
+__device__ __forceinline__ void dia_const_rows(
+    const DiaConstPlanes<T, M>& planes, const int64_t* __restrict__ offs,
+    int Wrt, const XWindow<T>& win0, const XWindow<T>& win1, Comb comb,
+    int64_t m, int64_t row0, int64_t col_lo, int64_t rbase, int64_t rhi,
+    Pre pre, Post post) {
+  constexpr int KB = WC ? WC : 8;  // diagonals per load batch
+  constexpr int64_t S = 2 * (int64_t)BLK * R;
+  const int W = WC ? WC : Wrt;
+  const int64_t lim = min(m, rhi);
+  const int64_t rb = rbase + (int64_t)blockIdx.x * S;
+  const int64_t t2 = 2 * (int64_t)threadIdx.x;
+  // own-piece index of row rb's main-diagonal column
+  const int64_t cb = row0 + rb - col_lo - win0.nlo;
+  const int64_t own_end = min(win0.nown, win0.wsize - win0.nlo);
+  // the first batch's offsets and constants, in registers before any load
+  int64_t o[KB];
+  T c[KB];
+#pragma unroll
+  for (int i = 0; i < KB; ++i) {
+    if (i < W) {
+      o[i] = offs[i];
+      c[i] = planes.cvals[i];
+    }
+  }
+  const bool interior = rb + S <= lim && cb + o[0] >= 0 &&
+                        cb + (S - 1) + (WC ? o[KB - 1] : offs[W - 1]) < own_end;
+  if (interior) {
+    using M2 = typename UIntOf<2 * sizeof(M)>::type;
+    M2 mw[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      mw[j] = nt_load(
+          reinterpret_cast<const M2*>(planes.mask + rb + t2 + j * 2 * BLK));
+    }
+    T a[R][2];
+#pragma unroll
+    for (int j = 0; j < R; ++j) a[j][0] = a[j][1] = ZeroOf<T>::value();
+    for (int k0 = 0; k0 < W; k0 += KB) {
+      if (k0 > 0) {
+#pragma unroll
+        for (int i = 0; i < KB; ++i) {
+          if (k0 + i < W) {
+            o[i] = offs[k0 + i];
+            c[i] = planes.cvals[k0 + i];
+          }
+        }
+      }
+      T xv[NWIN][R][KB][2];
+#pragma unroll
+      for (int i = 0; i < KB; ++i) {
+        if (k0 + i < W) {
+#pragma unroll
+          for (int w = 0; w < NWIN; ++w) {
+            // block-uniform address of the block's first column
+            const T* ub = (w == 0 ? win0 : win1).own + (cb + o[i]);
+            const bool aligned =
+                (reinterpret_cast<uintptr_t>(ub) % sizeof(Pair<T>)) == 0;
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+              const T* p = ub + t2 + j * 2 * BLK;
+              if (aligned) {
+                const Pair<T> t = *reinterpret_cast<const Pair<T>*>(p);
+                xv[w][j][i][0] = t.a;
+                xv[w][j][i][1] = t.b;
+              } else {
+                xv[w][j][i][0] = p[0];
+                xv[w][j][i][1] = p[1];
+              }
+            }
+          }
+        }
+      }
+      if (k0 == 0) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) pre(j, rb + t2 + j * 2 * BLK, true);
+        // keep the scheduler from sinking loads below the first use
+        __builtin_amdgcn_sched_barrier(0);
+      }
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const uint32_t m0 = (uint32_t)(M)mw[j];
+        const uint32_t m1 = (uint32_t)(mw[j] >> (8 * sizeof(M)));
+#pragma unroll
+        for (int i = 0; i < KB; ++i) {
+          if (k0 + i < W) {
+            T v0[NWIN], v1[NWIN];
+#pragma unroll
+            for (int w = 0; w < NWIN; ++w) {
+              v0[w] = xv[w][j][i][0];
+              v1[w] = xv[w][j][i][1];
+            }
+            const uint32_t bit = 1u << (k0 + i);
+            a[j][0] = fmadd((m0 & bit) ? c[i] : T(0), comb(v0), a[j][0]);
+            a[j][1] = fmadd((m1 & bit) ? c[i] : T(0), comb(v1), a[j][1]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      post(j, rb + t2 + j * 2 * BLK, a[j][0], a[j][1], true);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const int64_t r0 = rb + t2 + j * 2 * BLK;
+      if (r0 < rhi) {
+        T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
+        pre(j, r0, r0 + 1 < lim);
+        dia_accumulate(
+            planes, offs, W, r0, row0 + r0 - col_lo,
+            [&](int64_t c0, T& x0, T& x1) {
+              T v0[NWIN], v1[NWIN];
+#pragma unroll
+              for (int w = 0; w < NWIN; ++w) {
+                (w == 0 ? win0 : win1)
+                    .template pair<SINGLE, true>(c0, v0[w], v1[w]);
+              }
+              x0 = comb(v0);
+              x1 = comb(v1);
+            },
+            a0, a1);
+        post(j, r0, a0, a1, r0 + 1 < lim);
+      }
+    }
+  }
+}
+
+template <typename T, typename M, int WC, bool FUSE_DOT, bool SINGLE,
+          bool RESID>
+__global__ __launch_bounds__(BLK) void dia_const_spmv_kernel(
+    const DiaConstPlanes<T, M> planes, const int64_t* __restrict__ offs,
+    const XWindow<T> win, T* __restrict__ y, const T* __restrict__ pvec,
+    T* __restrict__ dot_partial, int64_t m, int W, int64_t col_lo,
+    int64_t row0, int64_t rbase, int64_t rhi) {
+  constexpr int R = kDiaPairs;
+  const int64_t lim = min(m, rhi);
+  Pair<T> pv[R];  // p (FUSE_DOT) or b (RESID) of the pair's rows
+  T d[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    pv[j] = Pair<T>{T(0), T(0)};
+    d[j] = T(0);
+  }
+  dia_const_rows<WC, R, SINGLE, 1>(
+      planes, offs, W, win, win, [](const T(&v)[1]) { return v[0]; }, m,
+      row0, col_lo, rbase, rhi,
+      [&](int j, int64_t r0, bool full) {
+        if (FUSE_DOT || RESID) {
+          if (full) {
+            pv[j] = *reinterpret_cast<const Pair<T>*>(&pvec[r0]);
+          } else if (r0 < lim) {
+            pv[j].a = pvec[r0];
+          }
+        }
+      },
+      [&](int j, int64_t r0, T a0, T a1, bool full) {
+        if (RESID) {
+          // y = b - A x: the V-cycle residual fused into the SpMV
+          a0 = pv[j].a - a0;
+          a1 = pv[j].b - a1;
+        }
+        if (full) {
+          *reinterpret_cast<Pair<T>*>(&y[r0]) = Pair<T>{a0, a1};
+        } else {
+          store_pair_or_tail(y, r0, m, rhi, a0, a1);
+        }
+        if (FUSE_DOT) {
+          T dd = T(0);
+          if (full || r0 < lim) dd = fmadd(a0, pv[j].a, dd);
+          if (full) dd = fmadd(a1, pv[j].b, dd);
+          d[j] = dd;
+        }
+      });
+  if (FUSE_DOT) {
+    const T sum = block_sums_256<R>(d);
+    const int64_t slot = (int64_t)blockIdx.x * R + threadIdx.x;
+    if (threadIdx.x < R && slot * (2 * BLK) < rhi - rbase) {
+      dot_partial[slot] = sum;
+    }
+  }
+}
+
+template <typename T, typename M, int WC, bool SINGLE>
+__global__ __launch_bounds__(BLK) void dia_const_jacobi_kernel(
+    const DiaConstPlanes<T, M> planes, const int64_t* __restrict__ offs,
+    const XWindow<T> win, const T* __restrict__ xloc,
+    const T* __restrict__ b, const T* __restrict__ dinv,
+    T* __restrict__ xout, int64_t m, int W, int64_t col_lo, int64_t row0,
+    T omega, int64_t rbase, int64_t rhi) {
+  constexpr int R = kDiaPairs;
+  Pair<T> xv[R], bv[R], dv[R];
+  dia_const_rows<WC, R, SINGLE, 1>(
+      planes, offs, W, win, win, [](const T(&v)[1]) { return v[0]; }, m,
+      row0, col_lo, rbase, rhi,
+      [&](int j, int64_t r0, bool full) {
+        if (full) {
+          xv[j] = *reinterpret_cast<const Pair<T>*>(&xloc[r0]);
+          bv[j] = *reinterpret_cast<const Pair<T>*>(&b[r0]);
+          dv[j] = *reinterpret_cast<const Pair<T>*>(&dinv[r0]);
+        }
+      },
+      [&](int j, int64_t r0, T a0, T a1, bool full) {
+        if (full) {
+          *reinterpret_cast<Pair<T>*>(&xout[r0]) =
+              Pair<T>{fmadd(omega * dv[j].a, bv[j].a - a0, xv[j].a),
+                      fmadd(omega * dv[j].b, bv[j].b - a1, xv[j].b)};
+        } else {
+          jacobi_update(xloc, b, dinv, xout, omega, r0, m, rhi, a0, a1);
+        }
+      });
+}
+
+// dia_spmv_bpdot_kernel on the constant-plane source
+template <typename T, typename M, int WC, bool SINGLE>
+__global__ __launch_bounds__(BLK) void dia_const_bpdot_kernel(
+    const DiaConstPlanes<T, M> planes, const int64_t* __restrict__ offs,
+    const XWindow<T> rwin, const XWindow<T> pwin, T* __restrict__ pnew,
+    T* __restrict__ q, const T* __restrict__ beta_num,
+    const T* __restrict__ beta_den, T* __restrict__ dot_partial, int64_t m,
+    int64_t mp, int W, int64_t col_lo, int64_t row0) {
+  constexpr int R = kDiaBpdotPairs;
+  const T beta = (*beta_num) / (*beta_den);
+  auto comb = [&](const T(&v)[2]) { return fmadd(beta, v[1], v[0]); };
+  T rr[R][2], pp[R][2];  // own rows of r and p_old
+  T d[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) d[j] = T(0);
+  dia_const_rows<WC, R, SINGLE, 2>(
+      planes, offs, W, rwin, pwin, comb, m, row0, col_lo, 0, mp,
+      [&](int j, int64_t r0, bool) {
+        // clamped like the streamed kernel's: offset 0 need not be a
+        // diagonal, and row r0 + 1 of a lone tail is loaded but never used
+        const int64_t c0 = row0 + r0 - col_lo;
+        rwin.template pair<SINGLE, true>(c0, rr[j][0], rr[j][1]);
+        pwin.template pair<SINGLE, true>(c0, pp[j][0], pp[j][1]);
+      },
+      [&](int j, int64_t r0, T a0, T a1, bool full) {
+        // own-row p_new: the formula of the window recompute, same bits
+        const T v0[2] = {rr[j][0], pp[j][0]}, v1[2] = {rr[j][1], pp[j][1]};
+        const T p0 = comb(v0), p1 = comb(v1);
+        if (full) {
+          *reinterpret_cast<Pair<T>*>(&pnew[r0]) = Pair<T>{p0, p1};
+          *reinterpret_cast<Pair<T>*>(&q[r0]) = Pair<T>{a0, a1};
+        } else {
+          store_pair_or_tail(pnew, r0, m, m, p0, p1);
+          store_pair_or_tail(q, r0, m, m, a0, a1);
+        }
+        T dd = T(0);
+        if (full || r0 < m) dd = fmadd(a0, p0, dd);
+        if (full) dd = fmadd(a1, p1, dd);
+        d[j] = dd;
+      });
+  const T sum = block_sums_256<R>(d);
+  const int64_t slot = (int64_t)blockIdx.x * R + threadIdx.x;
+  if (threadIdx.x < R && slot * (2 * BLK) < mp) dot_partial[slot] = sum;
 }
 
 // blocks of BLK threads covering `span` rows, two rows per thread
@@ -823,6 +1125,14 @@ struct RowPairLaunch {
   void launch(void (*kern)(P...), A... args) const {
     hipLaunchKernelGGL(kern, dim3(nblocks), dim3(BLK), 0, cur_stream(),
                        static_cast<P>(args)...);
+  }
+
+  // kernels whose threads own R row pairs: nblocks stays the number of
+  // 2 * BLK row groups (and of dot partials), the grid shrinks by R
+  template <int R, typename... P, typename... A>
+  void launch_pairs(void (*kern)(P...), A... args) const {
+    hipLaunchKernelGGL(kern, dim3((nblocks + R - 1) / R), dim3(BLK), 0,
+                       cur_stream(), static_cast<P>(args)...);
   }
 };
 
@@ -867,6 +1177,31 @@ void dispatch_dia_planes(const at::Tensor& planes, const OptTensor& mask,
   }
   TORCH_CHECK(false, "dia: constant planes need a real value type and a "
                      "uint8/uint16/uint32 row mask");
+}
+
+template <typename P>
+struct DiaConstOf : std::false_type {};
+template <typename T, typename M>
+struct DiaConstOf<DiaConstPlanes<T, M>> : std::true_type {
+  using mask_t = M;
+};
+
+// f(integral_constant WC) for the constant-plane kernels: W itself under a
+// u8 mask (1 <= W <= 8), 0 (run-time W) under the wider masks
+template <typename M, typename F>
+void dispatch_dia_wc(int64_t W, F&& f) {
+  TORCH_CHECK(W >= 1, "dia: at least one diagonal expected");
+  if constexpr (std::is_same_v<M, uint8_t>) {
+    switch (W) {
+#define SPARSE_DIA_WC(N) \
+  case N: f(std::integral_constant<int, N>{}); return;
+      SPARSE_DIA_WC(1) SPARSE_DIA_WC(2) SPARSE_DIA_WC(3) SPARSE_DIA_WC(4)
+      SPARSE_DIA_WC(5) SPARSE_DIA_WC(6) SPARSE_DIA_WC(7) SPARSE_DIA_WC(8)
+#undef SPARSE_DIA_WC
+      default: break;
+    }
+  }
+  f(std::integral_constant<int, 0>{});
 }
 
 }  // namespace
@@ -1045,13 +1380,27 @@ static at::Tensor dia_spmv_impl(const at::Tensor& planes, const OptTensor& mask,
     dispatch_dia_planes<T>(planes, mask, W, [&](auto pl) {
       dispatch_bool(fuse_dot, [&](auto fuse) {
         dispatch_bool(L.single, [&](auto single) {
-          if constexpr (!(RESID && decltype(fuse)::value)) {
-            L.launch(dia_spmv_kernel<T, decltype(pl), decltype(fuse)::value,
+          using PL = decltype(pl);
+          const T* pp = pvec ? pvec->data_ptr<T>() : nullptr;
+          T* dp = fuse_dot ? partial.data_ptr<T>() : nullptr;
+          if constexpr (RESID && decltype(fuse)::value) {
+          } else if constexpr (DiaConstOf<PL>::value) {
+            using M = typename DiaConstOf<PL>::mask_t;
+            dispatch_dia_wc<M>(W, [&](auto wc) {
+              L.launch_pairs<kDiaPairs>(
+                  dia_const_spmv_kernel<T, M, decltype(wc)::value,
+                                        decltype(fuse)::value,
+                                        decltype(single)::value, RESID>,
+                  pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
+                  y.data_ptr<T>(), pp, dp, m, W, col_lo, row0, L.rbase,
+                  L.rhi);
+            });
+          } else {
+            L.launch(dia_spmv_kernel<T, PL, decltype(fuse)::value,
                                      decltype(single)::value, RESID>,
                      pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
-                     y.data_ptr<T>(), pvec ? pvec->data_ptr<T>() : nullptr,
-                     fuse_dot ? partial.data_ptr<T>() : nullptr, m, L.mp, W,
-                     col_lo, row0, L.rbase, L.rhi);
+                     y.data_ptr<T>(), pp, dp, m, L.mp, W, col_lo, row0,
+                     L.rbase, L.rhi);
           }
         });
       });
@@ -1102,11 +1451,25 @@ void dia_jacobi_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
     using T = scalar_t;
     dispatch_dia_planes<T>(planes, mask, W, [&](auto pl) {
       dispatch_bool(L.single, [&](auto single) {
-        L.launch(dia_jacobi_kernel<T, decltype(pl), decltype(single)::value>,
-                 pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
-                 xloc.data_ptr<T>(), b.data_ptr<T>(), dinv.data_ptr<T>(),
-                 xout.data_ptr<T>(), m, L.mp, W, col_lo, row0, omega, L.rbase,
-                 L.rhi);
+        using PL = decltype(pl);
+        if constexpr (DiaConstOf<PL>::value) {
+          using M = typename DiaConstOf<PL>::mask_t;
+          dispatch_dia_wc<M>(W, [&](auto wc) {
+            L.launch_pairs<kDiaPairs>(
+                dia_const_jacobi_kernel<T, M, decltype(wc)::value,
+                                        decltype(single)::value>,
+                pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
+                xloc.data_ptr<T>(), b.data_ptr<T>(), dinv.data_ptr<T>(),
+                xout.data_ptr<T>(), m, W, col_lo, row0, omega, L.rbase,
+                L.rhi);
+          });
+        } else {
+          L.launch(dia_jacobi_kernel<T, PL, decltype(single)::value>, pl,
+                   offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
+                   xloc.data_ptr<T>(), b.data_ptr<T>(), dinv.data_ptr<T>(),
+                   xout.data_ptr<T>(), m, L.mp, W, col_lo, row0, omega,
+                   L.rbase, L.rhi);
+        }
       });
     });
   });
@@ -1130,13 +1493,26 @@ at::Tensor dia_spmv_bpdot_hip(at::Tensor planes, OptTensor mask,
     using T = scalar_t;
     dispatch_dia_planes<T>(planes, mask, W, [&](auto pl) {
       dispatch_bool(L.single, [&](auto single) {
-        L.launch(dia_spmv_bpdot_kernel<T, decltype(pl), decltype(single)::value>,
-                 pl, offs.data_ptr<int64_t>(),
+        using PL = decltype(pl);
+        auto go = [&](auto launch, auto kern) {
+          launch(kern, pl, offs.data_ptr<int64_t>(),
                  L.window<T>(r_hlo, r_own, r_hhi),
                  L.window<T>(p_hlo, p_own, p_hhi), pnew.data_ptr<T>(),
                  q.data_ptr<T>(), beta_num.data_ptr<T>(),
                  beta_den.data_ptr<T>(), partial.data_ptr<T>(), m, L.mp, W,
                  col_lo, row0);
+        };
+        if constexpr (DiaConstOf<PL>::value) {
+          using M = typename DiaConstOf<PL>::mask_t;
+          dispatch_dia_wc<M>(W, [&](auto wc) {
+            go([&](auto... a) { L.launch_pairs<kDiaBpdotPairs>(a...); },
+               dia_const_bpdot_kernel<T, M, decltype(wc)::value,
+                                      decltype(single)::value>);
+          });
+        } else {
+          go([&](auto... a) { L.launch(a...); },
+             dia_spmv_bpdot_kernel<T, PL, decltype(single)::value>);
+        }
       });
     });
   });
