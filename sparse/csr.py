@@ -445,6 +445,10 @@ class csr_array(CompressedBase, DenseSparseBase):
         self._dia_cache = None
         self._bsr_cache = None
         self._csc_cache = None
+        # plans that hold values (triangular-solve analyses) go with them;
+        # the structure-only gather plans stay
+        self._plan_cache = {k: p for k, p in self._plan_cache.items()
+                            if k[0] != "trsv"}
 
     @property
     def indices(self) -> np.ndarray:

@@ -392,6 +392,21 @@ def cdist(XA, XB, out):
     ext().cdist(XA, XB, out)
 
 
+# -- triangular solve ---------------------------------------------------------
+def trsv_levels(indptr, indices, lower: bool):
+    """Dependency levels of a strict-triangle CSR (host tensors; one
+    sequential O(nnz) pass, CPU-dispatched)."""
+    return ext().trsv_levels(indptr, indices, bool(lower))
+
+
+def trsv_solve(ts, values, diag, b, x):
+    """x = T^-1 b over the analysis of a trisolve.TriangularSolver: one
+    launch per schedule segment on the current stream, no host sync.  x may
+    alias b."""
+    ext().trsv_solve(ts._indptr, ts._indices, values, diag, ts._order,
+                     ts._level_ptr, ts._sched, b, x)
+
+
 # -- device-DIA fast path -----------------------------------------------------
 _DIA_CONST_DTYPES = (torch.float32, torch.float64)
 

@@ -2,6 +2,8 @@
 //
 // Loaded via torch.ops.load_library from sparse/kernels/_build/sparse_hip.so;
 // Python wrappers live in sparse/kernels/__init__.py.
+#include <algorithm>
+
 #include <torch/library.h>
 
 #include <ATen/ATen.h>
@@ -85,6 +87,53 @@ void spgemm_nnz_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
 void spgemm_compute_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                         at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                         at::Tensor, at::Tensor, int64_t, int64_t);
+void trsv_solve_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                    at::Tensor, at::Tensor, at::Tensor, at::Tensor);
+
+// Dependency levels of a strict-triangle CSR, one sequential O(nnz) pass on
+// the host (setup path of sparse/trisolve.py): levels[i] = 0 for a row with
+// no strict entries, else 1 + max(levels[j]) over its columns j.  Rows are
+// walked top-down for a lower triangle and bottom-up for an upper one, so
+// every levels[j] read is final.  A device relaxation or frontier peeling
+// would cost nlevels passes, and nlevels can equal n.
+template <typename I>
+static void trsv_levels_impl(const int64_t* ip, const I* ix, int64_t n,
+                             bool lower, int64_t* lv) {
+  for (int64_t s = 0; s < n; ++s) {
+    const int64_t i = lower ? s : n - 1 - s;
+    int64_t l = 0;
+    for (int64_t p = ip[i]; p < ip[i + 1]; ++p) {
+      const int64_t j = static_cast<int64_t>(ix[p]);
+      TORCH_CHECK(lower ? (0 <= j && j < i) : (i < j && j < n),
+                  "trsv_levels: entry outside the strict triangle");
+      l = std::max(l, lv[j] + 1);
+    }
+    lv[i] = l;
+  }
+}
+
+at::Tensor trsv_levels_cpu(at::Tensor indptr, at::Tensor indices, bool lower) {
+  TORCH_CHECK(indptr.scalar_type() == at::kLong && indptr.numel() >= 1 &&
+                  indptr.is_contiguous() && indices.is_contiguous(),
+              "trsv_levels: bad structure tensors");
+  const int64_t n = indptr.numel() - 1;
+  const int64_t* ip = indptr.data_ptr<int64_t>();
+  TORCH_CHECK(ip[0] == 0 && ip[n] == indices.numel(),
+              "trsv_levels: indptr does not match indices");
+  for (int64_t i = 0; i < n; ++i)
+    TORCH_CHECK(ip[i] <= ip[i + 1], "trsv_levels: indptr not monotone");
+  at::Tensor levels = at::zeros({n}, indptr.options());
+  if (indices.scalar_type() == at::kInt) {
+    trsv_levels_impl(ip, indices.data_ptr<int32_t>(), n, lower,
+                     levels.data_ptr<int64_t>());
+  } else {
+    TORCH_CHECK(indices.scalar_type() == at::kLong,
+                "trsv_levels: indices must be int32 or int64");
+    trsv_levels_impl(ip, indices.data_ptr<int64_t>(), n, lower,
+                     levels.data_ptr<int64_t>());
+  }
+  return levels;
+}
 
 TORCH_LIBRARY(sparse_hip, m) {
   m.def("spmv(Tensor indptr, Tensor indices, Tensor values, Tensor x, "
@@ -175,6 +224,10 @@ TORCH_LIBRARY(sparse_hip, m) {
   m.def("spgemm_compute(Tensor aip, Tensor aix, Tensor av, Tensor bip, "
         "Tensor bix, Tensor bv, Tensor rowlist, Tensor cip, Tensor(a!) cix, "
         "Tensor(b!) cv, int a_col_lo, int hash_size) -> ()");
+  m.def("trsv_solve(Tensor indptr, Tensor indices, Tensor values, "
+        "Tensor diag, Tensor order, Tensor level_ptr, Tensor sched, Tensor b, "
+        "Tensor(a!) x) -> ()");
+  m.def("trsv_levels(Tensor indptr, Tensor indices, bool lower) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
@@ -214,4 +267,9 @@ TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
   m.impl("cdist", cdist_hip);
   m.impl("spgemm_nnz", spgemm_nnz_hip);
   m.impl("spgemm_compute", spgemm_compute_hip);
+  m.impl("trsv_solve", trsv_solve_hip);
+}
+
+TORCH_LIBRARY_IMPL(sparse_hip, CPU, m) {
+  m.impl("trsv_levels", trsv_levels_cpu);
 }

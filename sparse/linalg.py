@@ -31,7 +31,8 @@ from .parallel import comm
 __all__ = [
     "LinearOperator", "IdentityOperator", "aslinearoperator", "cg", "cgs",
     "bicg", "bicgstab", "gmres", "minres", "lsqr", "eigsh", "svds",
-    "spsolve", "cg_axpby", "norm",
+    "spsolve", "cg_axpby", "norm", "spsolve_triangular", "TriangularSolver",
+    "sgs_preconditioner",
 ]
 
 
@@ -990,3 +991,9 @@ def eigsh(a, k=6, which="LM", ncv=None, maxiter=None, tol=0.0):
     X = np.stack([np.asarray(DistArray.from_local(ritz[c], V.part, V.vshape))
                   for c in range(k)], axis=1)
     return wk, X
+
+
+# -- triangular solves (level-scheduled; sparse/trisolve.py) -----------------
+from .trisolve import (  # noqa: E402,F401
+    TRSV_CHAIN_WIDTH, TriangularSolver, sgs_preconditioner,
+    spsolve_triangular)
