@@ -407,6 +407,17 @@ def trsv_solve(ts, values, diag, b, x):
                      ts._level_ptr, ts._sched, b, x)
 
 
+# -- ILU(0) ---------------------------------------------------------------------
+def ilu0_factor(fac, values, flag):
+    """Numeric ILU(0) in place in `values` over the analysis of an ilu.ILU0:
+    on the GPU one launch per schedule segment on the current stream, no
+    host sync; on host tensors the sequential CPU op.  flag (one int64 word,
+    preset >= n) receives the smallest row index with a zero pivot."""
+    ls = fac._Ls
+    ext().ilu0_factor(fac._indptr, fac._indices, values, fac._diag_ptr,
+                      ls._order, ls._level_ptr, fac._sched, flag)
+
+
 # -- device-DIA fast path -----------------------------------------------------
 _DIA_CONST_DTYPES = (torch.float32, torch.float64)
 

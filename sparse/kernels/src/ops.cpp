@@ -89,6 +89,8 @@ void spgemm_compute_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                         at::Tensor, at::Tensor, int64_t, int64_t);
 void trsv_solve_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, at::Tensor);
+void ilu0_factor_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                     at::Tensor, at::Tensor, at::Tensor, at::Tensor);
 
 // Dependency levels of a strict-triangle CSR, one sequential O(nnz) pass on
 // the host (setup path of sparse/trisolve.py): levels[i] = 0 for a row with
@@ -133,6 +135,68 @@ at::Tensor trsv_levels_cpu(at::Tensor indptr, at::Tensor indices, bool lower) {
                      levels.data_ptr<int64_t>());
   }
   return levels;
+}
+
+// Sequential IKJ ILU(0) on the host, in place in v (the host twin of
+// ilu0.hip; backs sparse/ilu.py without a GPU).  Rows are column-sorted and
+// duplicate-free with a stored diagonal at dp[i]; the update of one k is a
+// two-pointer merge of row i past k with row k past its diagonal.  Returns
+// the first row whose pivot is exactly zero, or n.
+template <typename T, typename I>
+static int64_t ilu0_factor_impl(const int64_t* ip, const I* ix, T* v,
+                                const int64_t* dp, int64_t n) {
+  int64_t bad = n;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t pe = ip[i + 1];
+    TORCH_CHECK(ip[i] <= dp[i] && dp[i] < pe &&
+                    static_cast<int64_t>(ix[dp[i]]) == i,
+                "ilu0_factor: diag_ptr does not point at the diagonal");
+    for (int64_t q = ip[i]; q < dp[i]; ++q) {
+      const int64_t k = static_cast<int64_t>(ix[q]);
+      TORCH_CHECK(0 <= k && k < i, "ilu0_factor: rows must be column-sorted");
+      const T m = v[q] / v[dp[k]];
+      v[q] = m;
+      int64_t p = q + 1;
+      for (int64_t t = dp[k] + 1; t < ip[k + 1] && p < pe; ++t) {
+        while (p < pe && ix[p] < ix[t]) ++p;
+        if (p < pe && ix[p] == ix[t]) v[p] -= m * v[t];
+      }
+    }
+    if (bad == n && v[dp[i]] == T(0)) bad = i;
+  }
+  return bad;
+}
+
+void ilu0_factor_cpu(at::Tensor indptr, at::Tensor indices, at::Tensor values,
+                     at::Tensor diag_ptr, at::Tensor /*order*/,
+                     at::Tensor /*level_ptr*/, at::Tensor /*sched*/,
+                     at::Tensor flag) {
+  TORCH_CHECK(indptr.scalar_type() == at::kLong && indptr.numel() >= 1 &&
+                  indptr.is_contiguous() && indices.is_contiguous() &&
+                  values.is_contiguous() && diag_ptr.is_contiguous() &&
+                  diag_ptr.scalar_type() == at::kLong &&
+                  flag.scalar_type() == at::kLong && flag.numel() == 1,
+              "ilu0_factor: bad structure tensors");
+  const int64_t n = indptr.numel() - 1;
+  const int64_t* ip = indptr.data_ptr<int64_t>();
+  TORCH_CHECK(ip[0] == 0 && ip[n] == indices.numel() &&
+                  indices.numel() == values.numel() && diag_ptr.numel() == n,
+              "ilu0_factor: indptr does not match indices");
+  for (int64_t i = 0; i < n; ++i)
+    TORCH_CHECK(ip[i] <= ip[i + 1], "ilu0_factor: indptr not monotone");
+  const bool i32 = indices.scalar_type() == at::kInt;
+  TORCH_CHECK(i32 || indices.scalar_type() == at::kLong,
+              "ilu0_factor: indices must be int32 or int64");
+  int64_t bad = n;
+  AT_DISPATCH_FLOATING_AND_COMPLEX_TYPES(
+      values.scalar_type(), "ilu0_factor", [&] {
+        scalar_t* v = values.data_ptr<scalar_t>();
+        const int64_t* dp = diag_ptr.data_ptr<int64_t>();
+        bad = i32 ? ilu0_factor_impl(ip, indices.data_ptr<int32_t>(), v, dp, n)
+                  : ilu0_factor_impl(ip, indices.data_ptr<int64_t>(), v, dp, n);
+      });
+  int64_t* fl = flag.data_ptr<int64_t>();
+  if (bad < n) fl[0] = std::min(fl[0], bad);
 }
 
 TORCH_LIBRARY(sparse_hip, m) {
@@ -228,6 +292,9 @@ TORCH_LIBRARY(sparse_hip, m) {
         "Tensor diag, Tensor order, Tensor level_ptr, Tensor sched, Tensor b, "
         "Tensor(a!) x) -> ()");
   m.def("trsv_levels(Tensor indptr, Tensor indices, bool lower) -> Tensor");
+  m.def("ilu0_factor(Tensor indptr, Tensor indices, Tensor(a!) values, "
+        "Tensor diag_ptr, Tensor order, Tensor level_ptr, Tensor sched, "
+        "Tensor(b!) flag) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
@@ -268,8 +335,10 @@ TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
   m.impl("spgemm_nnz", spgemm_nnz_hip);
   m.impl("spgemm_compute", spgemm_compute_hip);
   m.impl("trsv_solve", trsv_solve_hip);
+  m.impl("ilu0_factor", ilu0_factor_hip);
 }
 
 TORCH_LIBRARY_IMPL(sparse_hip, CPU, m) {
   m.impl("trsv_levels", trsv_levels_cpu);
+  m.impl("ilu0_factor", ilu0_factor_cpu);
 }

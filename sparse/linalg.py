@@ -32,7 +32,7 @@ __all__ = [
     "LinearOperator", "IdentityOperator", "aslinearoperator", "cg", "cgs",
     "bicg", "bicgstab", "gmres", "minres", "lsqr", "eigsh", "svds",
     "spsolve", "cg_axpby", "norm", "spsolve_triangular", "TriangularSolver",
-    "sgs_preconditioner",
+    "sgs_preconditioner", "ilu0", "ILU0",
 ]
 
 
@@ -997,3 +997,6 @@ def eigsh(a, k=6, which="LM", ncv=None, maxiter=None, tol=0.0):
 from .trisolve import (  # noqa: E402,F401
     TRSV_CHAIN_WIDTH, TriangularSolver, sgs_preconditioner,
     spsolve_triangular)
+
+# -- ILU(0) preconditioner (sparse/ilu.py) -------------------------------------
+from .ilu import ILU0, ilu0  # noqa: E402,F401

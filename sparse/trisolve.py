@@ -189,6 +189,16 @@ class TriangularSolver(LinearOperator):
         return [("chain" if c else "wide", int(lo), int(hi))
                 for c, lo, hi in zip(chain, starts, ends)]
 
+    def _set_values(self, values: torch.Tensor,
+                    diag: Optional[torch.Tensor] = None) -> None:
+        """New strict-triangle values (and diagonal) on the unchanged
+        structure, copied into the solver's own arrays; the analysis stays
+        (ILU0.refactor in sparse/ilu.py)."""
+        self._values.copy_(values)
+        if diag is not None:
+            self._diag.copy_(diag)
+        self._cast.clear()
+
     # -- solve ----------------------------------------------------------------
     def _operands(self, tdt):
         if tdt == self._values.dtype:
