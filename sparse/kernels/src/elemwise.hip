@@ -169,6 +169,7 @@ void add_nnz_hip(at::Tensor aip, at::Tensor aix, at::Tensor bip, at::Tensor bix,
                        aix.data_ptr<index_t>(), bip.data_ptr<int64_t>(),
                        bix.data_ptr<index_t>(), out.data_ptr<int64_t>(), m);
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void add_compute_hip(at::Tensor aip, at::Tensor aix, at::Tensor av,
@@ -189,6 +190,7 @@ void add_compute_hip(at::Tensor aip, at::Tensor aix, at::Tensor av,
                          static_cast<T>(alpha), static_cast<T>(beta));
     });
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void mult_nnz_hip(at::Tensor aip, at::Tensor aix, at::Tensor bip, at::Tensor bix,
@@ -201,6 +203,7 @@ void mult_nnz_hip(at::Tensor aip, at::Tensor aix, at::Tensor bip, at::Tensor bix
                        aix.data_ptr<index_t>(), bip.data_ptr<int64_t>(),
                        bix.data_ptr<index_t>(), out.data_ptr<int64_t>(), m);
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void mult_compute_hip(at::Tensor aip, at::Tensor aix, at::Tensor av,
@@ -219,6 +222,7 @@ void mult_compute_hip(at::Tensor aip, at::Tensor aix, at::Tensor av,
                          cix.data_ptr<index_t>(), cv.data_ptr<T>(), m);
     });
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void mult_dense_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
@@ -235,6 +239,7 @@ void mult_dense_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
                          D.data_ptr<T>(), out.data_ptr<T>(), m, D.size(1), nnz);
     });
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void axpby_hip(at::Tensor y, at::Tensor x, at::Tensor a, at::Tensor b,

@@ -11,6 +11,11 @@
 //    stencil row otherwise leaves 59 of 64 lanes idle;
 //  - rows are emitted SORTED via an LDS bitonic over the compacted entries
 //    (no global argsort pass over C).
+// Static LDS: the largest instantiation is the complex128 compute kernel
+// with the 1024-entry table, 158,864 B per block (155,216 B with the
+// 2048-entry table) against the 163,840 B a CU has; the per-kernel sizes
+// are in profiles/spgemm_resources.txt.  A launch the runtime refuses
+// raises through SPARSE_CHECK_HIP in the host wrappers.
 #include "common.h"
 
 namespace {
@@ -252,6 +257,7 @@ void spgemm_nnz_hip(at::Tensor aip, at::Tensor aix, at::Tensor bip,
     else  // checked speculative bin: overflow -> nnz_out = -1
       launch(spgemm_nnz_kernel<index_t, 4096, 64, 1, true>, 1, 64);
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void spgemm_compute_hip(at::Tensor aip, at::Tensor aix, at::Tensor av,
@@ -291,4 +297,5 @@ void spgemm_compute_hip(at::Tensor aip, at::Tensor aix, at::Tensor av,
       }
     });
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }

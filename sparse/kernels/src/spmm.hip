@@ -244,4 +244,5 @@ void sddmm_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
                          m, D.size(1), Cm.size(1), nnz, col_lo);
     });
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }

@@ -174,7 +174,12 @@ def sddmm(A: LocalCSR, C: torch.Tensor, D: torch.Tensor,
 # -- elementwise --------------------------------------------------------------
 def add(A: LocalCSR, B: LocalCSR, alpha=1.0, beta=1.0) -> LocalCSR:
     """Union add alpha*A + beta*B on aligned row slabs, two-phase.
-    Reference: ADD_CSR_CSR_NNZ / ADD_CSR_CSR (add.cu)."""
+    Reference: ADD_CSR_CSR_NNZ / ADD_CSR_CSR (add.cu).
+
+    Structure: on the GPU the result holds the UNION of the two patterns,
+    rows sorted and duplicate-free; an entry whose value cancels to zero is
+    kept (as in the reference's two-phase kernels).  The scipy-backed CPU
+    branch drops such entries."""
     vdt = torch.promote_types(A.dtype, B.dtype)
     if is_gpu(A.values):
         return hip().add_csr(A, B, alpha, beta, vdt)
@@ -192,7 +197,12 @@ def _np_of(t: torch.dtype):
 
 
 def elem_mult(A: LocalCSR, B: LocalCSR) -> LocalCSR:
-    """Intersection multiply.  Reference: ELEM_MULT_CSR_CSR (mult.cu:27-109)."""
+    """Intersection multiply.  Reference: ELEM_MULT_CSR_CSR (mult.cu:27-109).
+
+    Structure: on the GPU the result holds the INTERSECTION of the two
+    patterns, rows sorted and duplicate-free, whatever the values (a product
+    that underflows to zero stays).  The scipy-backed CPU branch drops
+    entries whose value is exactly zero."""
     vdt = torch.promote_types(A.dtype, B.dtype)
     if is_gpu(A.values):
         return hip().elem_mult_csr(A, B, vdt)
@@ -220,7 +230,13 @@ def mult_dense(A: LocalCSR, D: torch.Tensor) -> torch.Tensor:
 def spgemm(A: LocalCSR, B: LocalCSR, a_col_lo: int = 0) -> LocalCSR:
     """C = A @ B where B holds rows [a_col_lo, a_col_lo + B.nrows) of the
     global B (gathered by the caller).  GPU: two-phase Gustavson hash.
-    Reference: SPGEMM_CSR_CSR_CSR_GPU (spgemm_csr_csr_csr.cu:33-272)."""
+    Reference: SPGEMM_CSR_CSR_CSR_GPU (spgemm_csr_csr_csr.cu:33-272).
+
+    Structure: on the GPU a row of C holds every column that at least one
+    product a_ik * b_kj touches, sorted and duplicate-free; an entry whose
+    products cancel to zero is kept (LDS tables, dense-workspace and
+    expand-sort-reduce fallbacks alike).  The scipy-backed CPU branch drops
+    such entries."""
     vdt = torch.promote_types(A.dtype, B.dtype)
     if is_gpu(A.values):
         return hip().spgemm_csr(A, B, a_col_lo, vdt)
