@@ -17,6 +17,40 @@ from .parallel.partition import RowPartition
 from .runtime import runtime
 
 
+def canonical_scipy(m):
+    """A scipy CSR / CSC matrix holding m's entries with strictly increasing
+    indices within every row (column): m itself when it already is so, else a
+    COPY with the duplicates summed and the indices sorted.  Explicit zeros
+    stay (a cancelling pair becomes a stored zero): they are part of the
+    pattern.  m is never modified.
+
+    Every kernel relies on this form; the constructors that take entries
+    from outside (scipy objects, (data, indices, indptr) triples) pass
+    through here.  The test is one host pass over the indices, a slab at a
+    time (no nnz-sized temporaries)."""
+    ix, ip = m.indices, m.indptr
+    if not _rows_strictly_increasing(ix, ip):
+        # a fresh object: it shares nothing with m and has no cached
+        # has_sorted_indices / has_canonical_format flags
+        m = type(m)((m.data.copy(), ix.copy(), ip.copy()), shape=m.shape)
+        m.sum_duplicates()
+    return m
+
+
+def _rows_strictly_increasing(ix, ip, slab=1 << 24):
+    n = ix.size
+    for s in range(1, n, slab):
+        e = min(s + slab, n)
+        # positions p in [s, e) that do not step up from p - 1 ...
+        bad = np.flatnonzero(ix[s:e] <= ix[s - 1: e - 1]) + s
+        if bad.size:
+            # ... are fine only as the first entry of a row
+            pos = np.minimum(np.searchsorted(ip, bad), ip.size - 1)
+            if not np.array_equal(ip[pos], bad):
+                return False
+    return True
+
+
 class CompressedBase:
     # numpy must defer binary ops to our reflected implementations
     __array_priority__ = 30.0
@@ -94,7 +128,8 @@ class CompressedBase:
         return s / denom
 
     # structures are always column-sorted and duplicate-free here (owner
-    # shuffles sort and sum on construction): scipy API compat no-ops
+    # shuffles sort and sum on construction, and input from outside is put
+    # into that form by canonical_scipy): scipy API compat no-ops
     has_sorted_indices = True
     has_canonical_format = True
 

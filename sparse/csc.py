@@ -18,7 +18,7 @@ import torch
 import scipy.sparse as _sps
 
 from .coverage import clone_scipy_arr_kind
-from .base import CompressedBase, DenseSparseBase
+from .base import CompressedBase, DenseSparseBase, canonical_scipy
 from .darray import DistArray, asdistarray
 from .ops import local as ops
 from .parallel import comm
@@ -50,8 +50,9 @@ class csc_array(CompressedBase, DenseSparseBase):
                                   arg.partition, arg.shape)
             return
         if isinstance(arg, (sps.spmatrix, sps.sparray)):
-            m = arg.tocsc()
-            m.sort_indices()
+            # tocsc() of a CSC input is the caller's own object: it is only
+            # read; duplicates and unsorted columns are fixed on a copy
+            m = canonical_scipy(arg.tocsc())
             gshape = m.shape if shape is None else tuple(shape)
             part = RowPartition.equal(gshape[1], comm.world_size())
             r = comm.rank()
@@ -122,6 +123,9 @@ class csc_array(CompressedBase, DenseSparseBase):
 
     @classmethod
     def from_local(cls, colptr, indices, values, partition, shape) -> "csc_array":
+        """Wrap one rank's slab as is.  The arrays are TRUSTED: columns must
+        be row-sorted and duplicate-free; only the constructors that take
+        entries from outside check and repair."""
         self = cls.__new__(cls)
         self._init_from_local(colptr, indices, values, partition, shape)
         return self

@@ -20,7 +20,7 @@ import torch
 import scipy.sparse as _sps
 
 from .coverage import clone_scipy_arr_kind
-from .base import CompressedBase, DenseSparseBase
+from .base import CompressedBase, DenseSparseBase, canonical_scipy
 from .darray import DistArray, asdistarray
 from .ops import local as ops
 from .parallel import comm
@@ -61,8 +61,9 @@ class csr_array(CompressedBase, DenseSparseBase):
         import scipy.sparse as sps
 
         if isinstance(arg, sps.spmatrix) or isinstance(arg, sps.sparray):
-            m = arg.tocsr()
-            m.sort_indices()
+            # tocsr() of a CSR input is the caller's own object: it is only
+            # read; duplicates and unsorted rows are fixed on a copy
+            m = canonical_scipy(arg.tocsr())
             gshape = m.shape if shape is None else shape
             part = _default_partition(gshape[0])
             r = comm.rank()
@@ -110,7 +111,8 @@ class csr_array(CompressedBase, DenseSparseBase):
                     indptr.numel() == _default_partition(shape[0]).count(comm.rank()) + 1
                     and indptr.numel() != shape[0] + 1
                 ):
-                    # already-local torch tensors (internal fast path)
+                    # already-local torch tensors (internal fast path):
+                    # trusted to be column-sorted and duplicate-free
                     part = _default_partition(shape[0])
                     self._init_from_local(indptr.to(torch.int64), indices, data, part, shape)
                     return
@@ -120,18 +122,11 @@ class csr_array(CompressedBase, DenseSparseBase):
                 m = indptr.shape[0] - 1
                 n = shape[1] if shape is not None else (int(indices.max()) + 1 if indices.size else 0)
                 gshape = (m, n) if shape is None else tuple(shape)
-                part = _default_partition(gshape[0])
-                r = comm.rank()
-                r0, r1 = part.start(r), part.stop(r)
-                lptr = indptr[r0: r1 + 1].astype(np.int64)
-                s, e = int(lptr[0]), int(lptr[-1])
-                idt = index_dtype_for(gshape)
-                vals = torch.as_tensor(np.ascontiguousarray(data[s:e]), device=rt.device)
-                vals = vals.to(tdtype) if tdtype else vals.to(promote_value_dtype(vals.dtype))
-                self._init_from_local(
-                    torch.as_tensor(lptr - s, dtype=torch.int64, device=rt.device),
-                    torch.as_tensor(np.ascontiguousarray(indices[s:e]), device=rt.device).to(idt),
-                    vals, part, gshape)
+                # same route as a scipy object: duplicates add up and rows
+                # come out sorted, the caller's arrays are only read
+                self.__init__(sps.csr_matrix((data, indices, indptr),
+                                             shape=gshape),
+                              shape=gshape, dtype=dtype)
                 return
             raise NotImplementedError(f"cannot construct csr_array from tuple of len {len(arg)}")
 
@@ -198,6 +193,9 @@ class csr_array(CompressedBase, DenseSparseBase):
 
     @classmethod
     def from_local(cls, indptr, indices, values, partition, shape) -> "csr_array":
+        """Wrap one rank's slab as is.  The arrays are TRUSTED: rows must be
+        column-sorted and duplicate-free (every kernel relies on it); only
+        the constructors that take entries from outside check and repair."""
         self = cls.__new__(cls)
         CompressedBase.__init__(self)
         self._init_from_local(indptr, indices, values, partition, shape)

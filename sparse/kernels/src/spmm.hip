@@ -177,6 +177,7 @@ void bsr_spmm_hip(at::Tensor bptr, at::Tensor bcol, at::Tensor bvals,
                        B.data_ptr<float>(), C.data_ptr<float>(), nbrows,
                        mrows, k, col_lo, nwin);
   }
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void spmm_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
@@ -207,6 +208,7 @@ void spmm_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
                          m, k, col_lo);
     });
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void rspmm_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
@@ -227,6 +229,7 @@ void rspmm_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
                          mloc, n, kd, nnz);
     });
   });
+  SPARSE_CHECK_HIP(hipGetLastError());
 }
 
 void sddmm_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
