@@ -432,13 +432,19 @@ class DiaMirror:
     keeps cvals (the W constants) and mask (one word per padded row, bit k
     set where plane k holds cvals[k]; uint8/16/32 for W <= 8/16/32).  The
     kernels read 1-4 B/row instead of W values and give bit-identical
-    results."""
+    results.
+    adj is the adjacency word of the offsets (bit i set where offs[i + 1] ==
+    offs[i] + 1): the constant-plane kernels take the pairs of adjacent
+    diagonals from each other's registers instead of loading them twice, and
+    choose that plan at launch from this word (the offsets themselves live
+    on the device)."""
 
     __slots__ = ("dvals", "offs", "W", "m", "row0", "off_min", "off_max",
-                 "cvals", "mask")
+                 "cvals", "mask", "adj")
 
     def __init__(self, dvals, offs, W, m, row0, off_min=0, off_max=0,
-                 cvals=None, mask=None):
+                 cvals=None, mask=None, adj=0):
+        self.adj = adj
         self.off_min = off_min
         self.off_max = off_max
         self.dvals = dvals
@@ -515,9 +521,11 @@ def build_dia(A, row0: int, compress: bool = True):
             dvals = None  # releases the planes
         else:
             cvals = mask = None
-    return DiaMirror(dvals, offs, W, m, row0,
-                     off_min=int(offs[0].item()), off_max=int(offs[-1].item()),
-                     cvals=cvals, mask=mask)
+    # one host read of the W offsets, here at mirror build only
+    ho = offs.tolist()
+    adj = sum(1 << i for i in range(min(W, 32) - 1) if ho[i + 1] == ho[i] + 1)
+    return DiaMirror(dvals, offs, W, m, row0, off_min=ho[0], off_max=ho[-1],
+                     cvals=cvals, mask=mask, adj=adj)
 
 
 def _pieces(p):
@@ -532,7 +540,8 @@ def dia_spmv(dm: DiaMirror, pieces, y, col_lo: int, wsize: int,
     interior/boundary split that overlaps halo exchange with interior
     compute at ws>1."""
     ext().dia_spmv(*dm.source(), dm.offs, *_pieces(pieces), y, dm.W, dm.m,
-                   int(col_lo), dm.row0, int(wsize), int(rbase), int(rhi))
+                   int(col_lo), dm.row0, int(wsize), int(rbase), int(rhi),
+                   dm.adj)
 
 
 def dia_spmv_dot(dm: DiaMirror, pieces, y, p, col_lo: int, wsize: int,
@@ -541,7 +550,7 @@ def dia_spmv_dot(dm: DiaMirror, pieces, y, p, col_lo: int, wsize: int,
     0-dim, local partial-sum; exact zero for an empty range)."""
     return ext().dia_spmv_dot(*dm.source(), dm.offs, *_pieces(pieces), y, p,
                               dm.W, dm.m, int(col_lo), dm.row0, int(wsize),
-                              int(rbase), int(rhi))
+                              int(rbase), int(rhi), dm.adj)
 
 
 def dia_spmv_bpdot(dm: DiaMirror, r_pieces, p_pieces, pnew, q,
@@ -553,7 +562,7 @@ def dia_spmv_bpdot(dm: DiaMirror, r_pieces, p_pieces, pnew, q,
     return ext().dia_spmv_bpdot(*dm.source(), dm.offs, *_pieces(r_pieces),
                                 *_pieces(p_pieces), pnew, q, beta_num,
                                 beta_den, dm.W, dm.m, int(col_lo), dm.row0,
-                                int(wsize))
+                                int(wsize), dm.adj)
 
 
 def cg_xr_norm2(x, p, r, q, a, b):
@@ -574,14 +583,14 @@ def dia_residual(dm: DiaMirror, pieces, b, y, col_lo: int, wsize: int,
     """Fused V-cycle residual y = b - A@x (x given as window pieces)."""
     ext().dia_residual(*dm.source(), dm.offs, *_pieces(pieces), b, y, dm.W,
                        dm.m, int(col_lo), dm.row0, int(wsize), int(rbase),
-                       int(rhi))
+                       int(rhi), dm.adj)
 
 
 def dia_jacobi(dm: DiaMirror, pieces, xloc, b, dinv, omega, xout,
                col_lo: int, wsize: int, rbase: int = 0, rhi: int = -1):
     ext().dia_jacobi(*dm.source(), dm.offs, *_pieces(pieces), xloc, b, dinv,
                      xout, dm.W, dm.m, int(col_lo), dm.row0, int(wsize),
-                     float(omega), int(rbase), int(rhi))
+                     float(omega), int(rbase), int(rhi), dm.adj)
 
 
 # -- BSR (MFMA) fast path -----------------------------------------------------

@@ -38,21 +38,22 @@ at::Tensor dia_spmv_bpdot_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
                               at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                               at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                               at::Tensor, int64_t, int64_t, int64_t, int64_t,
-                              int64_t);
+                              int64_t, int64_t);
 void dia_spmv_plain_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
                         at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
-                        int64_t, int64_t, int64_t, int64_t, int64_t);
+                        int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
 at::Tensor dia_spmv_dot_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
                             at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                             int64_t, int64_t, int64_t, int64_t, int64_t,
-                            int64_t, int64_t);
+                            int64_t, int64_t, int64_t);
 void dia_residual_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, at::Tensor, int64_t,
-                      int64_t, int64_t, int64_t, int64_t, int64_t, int64_t);
+                      int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                      int64_t);
 void dia_jacobi_hip(at::Tensor, OptTensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, int64_t, int64_t, int64_t, int64_t, int64_t,
-                    double, int64_t, int64_t);
+                    double, int64_t, int64_t, int64_t);
 void add_nnz_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor);
 void add_compute_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                      at::Tensor, at::Tensor, at::Tensor, at::Tensor, double,
@@ -240,24 +241,25 @@ TORCH_LIBRARY(sparse_hip, m) {
         "Tensor r_hlo, Tensor r_own, "
         "Tensor r_hhi, Tensor p_hlo, Tensor p_own, Tensor p_hhi, "
         "Tensor(a!) pnew, Tensor(b!) q, Tensor beta_num, Tensor beta_den, "
-        "int W, int m, int col_lo, int row0, int wsize) -> Tensor");
+        "int W, int m, int col_lo, int row0, int wsize, int adj=0) "
+        "-> Tensor");
   m.def("dia_spmv(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
         "Tensor own, "
         "Tensor hhi, Tensor(a!) y, int W, int m, int col_lo, int row0, "
-        "int wsize, int rbase, int rhi) -> ()");
+        "int wsize, int rbase, int rhi, int adj=0) -> ()");
   m.def("dia_spmv_dot(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
         "Tensor own, "
         "Tensor hhi, Tensor(a!) y, Tensor pvec, int W, int m, int col_lo, "
-        "int row0, int wsize, int rbase, int rhi) -> Tensor");
+        "int row0, int wsize, int rbase, int rhi, int adj=0) -> Tensor");
   m.def("dia_residual(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
         "Tensor own, "
         "Tensor hhi, Tensor b, Tensor(a!) y, int W, int m, int col_lo, "
-        "int row0, int wsize, int rbase, int rhi) -> ()");
+        "int row0, int wsize, int rbase, int rhi, int adj=0) -> ()");
   m.def("dia_jacobi(Tensor planes, Tensor? mask, Tensor offs, Tensor hlo, "
         "Tensor own, "
         "Tensor hhi, Tensor xloc, Tensor b, Tensor dinv, Tensor(a!) xout, "
         "int W, int m, int col_lo, int row0, int wsize, float omega, "
-        "int rbase, int rhi) -> ()");
+        "int rbase, int rhi, int adj=0) -> ()");
   m.def("spmm(Tensor indptr, Tensor indices, Tensor vals, Tensor B, "
         "Tensor(a!) C, int col_lo) -> ()");
   m.def("rspmm(Tensor indptr, Tensor indices, Tensor vals, Tensor A, "

@@ -799,8 +799,9 @@ __global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
 // ---------------------------------------------------------------------------
 // Constant-plane kernels.  Without a plane stream a wave moves ~2 KB per trip
 // through its dependent chain (mask -> x -> operands -> reduction), so these
-// kernels are bound by latency per wave, not by HBM
-// (profiles/dia_core_chain_profile.md).  dia_const_rows shortens the chain:
+// kernels are bound by latency per wave and by the number of vector loads a
+// wave issues, not by HBM (profiles/dia_core_chain_profile.md,
+// profiles/dia_lane_exchange_profile.md).  dia_const_rows shortens the chain:
 //  - a thread owns R row pairs, block-strided (pair j of thread t is rows
 //    rb + 2 * (t + j * BLK), so every wave instruction still touches one
 //    contiguous run) and issues the loads of all of them — mask words, the x
@@ -810,34 +811,257 @@ __global__ __launch_bounds__(BLK) void dia_spmv_bpdot_kernel(
 //    scalar wait sits between the x loads;
 //  - a block whose rows are all below min(m, rhi) and whose columns all lie
 //    in the own piece of the window (block-uniform test, scalar branch) uses
-//    plain addresses: one 16-byte load per x pair where the pair is aligned
-//    (uniform per diagonal, see XWindow::pair), two 8-byte loads otherwise.
+//    plain addresses (dia_const_interior): one 16-byte load per x pair where
+//    the pair is aligned (uniform per diagonal, see XWindow::pair), two
+//    8-byte loads otherwise, and no load at all for an unaligned pair next
+//    to an aligned one (lane exchange, below) or for a row operand that is
+//    the x slab itself.  The 5-pt stencil's fused p . A p so issues 10 loads
+//    per row-pair couple instead of 14.
 //    The other (edge) blocks run the clamped dia_accumulate above.
 // Per-row arithmetic is dia_accumulate's (a += v_k * x_k, k ascending): same
 // bits as the streamed planes.  The fused dot keeps ONE partial per 2 * BLK
 // rows, i.e. R per block, summed exactly like a block of the streamed
-// kernel: both value sources return the same dot bits.
-constexpr int kDiaPairs = 2;       // R of dia_spmv / residual / jacobi
-constexpr int kDiaBpdotPairs = 1;  // R of dia_spmv_bpdot (two windows)
+// kernel: both value sources return the same dot bits, whatever R is.
+// R: with the lane exchange in, R = 4 beats R = 2 on the 16384^2 5-pt SpMV
+// and its fused dot although it halves the occupancy (102 VGPRs, 4
+// waves/SIMD against 57 and 8); the residual and the Jacobi sweep carry
+// more operands per row (135 VGPRs at R = 4) and lose 7 % on the GMG
+// V-cycle there, so they stay at 2 (profiles/dia_lane_exchange_bench.txt).
+// More than 5 diagonals were not measured at R = 4 (W = 8 would need about
+// 150 VGPRs) and stay at 2 as well.
+constexpr int kDiaPairs = 4;        // R of dia_spmv and dia_spmv_dot, W <= 5
+constexpr int kDiaSmoothPairs = 2;  // R of dia_residual, dia_jacobi, W > 5
+constexpr int kDiaBpdotPairs = 1;   // R of dia_spmv_bpdot (two windows)
+
+// R of dia_const_spmv_kernel
+constexpr int dia_spmv_pairs(int WC, bool resid) {
+  return (!resid && WC >= 1 && WC <= 5) ? kDiaPairs : kDiaSmoothPairs;
+}
+
+// v of the next higher / lower lane of the wave (the last / first lane keeps
+// its own): one v_mov_b32 with a DPP wave shift per 32 bits.  Every lane of
+// the wave must be active.
+template <int CTRL, typename T>
+__device__ __forceinline__ T lane_shift(T v) {
+  static_assert(sizeof(T) % 4 == 0, "whole dwords expected");
+  int w[sizeof(T) / 4];
+  __builtin_memcpy(w, &v, sizeof(T));
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(T) / 4); ++i) {
+    w[i] = __builtin_amdgcn_update_dpp(w[i], w[i], CTRL, 0xf, 0xf, false);
+  }
+  __builtin_memcpy(&v, w, sizeof(T));
+  return v;
+}
+template <typename T>
+__device__ __forceinline__ T lane_above(T v) {
+  return lane_shift<0x130>(v);  // wave_shl:1
+}
+template <typename T>
+__device__ __forceinline__ T lane_below(T v) {
+  return lane_shift<0x138>(v);  // wave_shr:1
+}
+
+// Lane exchange.  Diagonals at consecutive offsets read overlapping pairs:
+// with (A_t, B_t) the pair of offset d in lane t, the pair of d + 1 is
+// (B_t, A_{t+1}) and that of d - 1 is (B_{t-1}, A_t).  Pairs alternate
+// between aligned and unaligned along such a run, so the unaligned ones
+// (a 16-byte load across two lines) are not loaded but taken from the
+// aligned neighbour's registers with a wave shift.  Only the wave's last
+// (first) lane lacks A_{t+1} (B_{t-1}); it fetches that one element with a
+// load in which no other lane is active.
+// ADJ is the compile-time plan: bit i says offs[i + 1] == offs[i] + 1, and
+// the set bits form one run (dispatch_dia_wc picks it from the mirror's
+// adjacency word; the kernel checks it against offs[] and sends a block
+// whose offsets disagree down the clamped path).  P is the run-time parity
+// of the run's first pair (0 aligned, 1 unaligned; -1 no exchange: ADJ == 0,
+// or two windows of different parity), resolved by one block-uniform branch
+// around the whole interior body so that every source below is static.
+enum DiaSrc { kDiaLoad, kDiaLoadAligned, kDiaFromLo, kDiaFromHi };
+
+template <uint32_t ADJ>
+struct DiaRun {
+  static constexpr int start = ADJ ? __builtin_ctz(ADJ) : 0;
+  static constexpr int len = ADJ ? __builtin_popcount(ADJ) + 1 : 1;
+  static_assert(ADJ == 0 || (ADJ >> start) + 1 == (1u << (len - 1)),
+                "the adjacent diagonals must form one run");
+  // where diagonal i's pair comes from
+  __host__ __device__ static constexpr DiaSrc src(int P, int i) {
+    const int q = i - start;
+    if (ADJ == 0 || P < 0 || q < 0 || q >= len) return kDiaLoad;
+    if (((P + q) & 1) == 0) return kDiaLoadAligned;
+    return q > 0 ? kDiaFromLo : kDiaFromHi;  // q == 0 borrows from q == 1
+  }
+  // diagonals i (from hi) and i + 2 (from lo) share one two-lane load
+  __host__ __device__ static constexpr bool two(int P, int i) {
+    return src(P, i) == kDiaFromHi && len >= 3;
+  }
+};
+
+// Interior block of dia_const_rows: rows rb .. rb + S - 1 are all below
+// min(m, rhi) and all their columns lie in the own piece, so addresses are
+// plain.  own[w] + cb is the address of row rb's main-diagonal column.
+template <int WC, int R, int NWIN, uint32_t ADJ, int P, typename T,
+          typename M, typename Comb, typename Pre, typename Post>
+__device__ __forceinline__ void dia_const_interior(
+    const DiaConstPlanes<T, M>& planes, const int64_t* __restrict__ offs,
+    int W, const T* const* own, Comb comb, bool ctr, int64_t rb,
+    int64_t cb, int64_t (&o)[WC ? WC : 8], T (&c)[WC ? WC : 8], Pre pre,
+    Post post) {
+  constexpr int KB = WC ? WC : 8;
+  using Run = DiaRun<ADJ>;
+  using M2 = typename UIntOf<2 * sizeof(M)>::type;
+  const int64_t t2 = 2 * (int64_t)threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  M2 mw[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    mw[j] = nt_load(
+        reinterpret_cast<const M2*>(planes.mask + rb + t2 + j * 2 * BLK));
+  }
+  T a[R][2];
+  Pair<T> cx[R];  // the offset-0 pair, for post (ctr)
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    a[j][0] = a[j][1] = ZeroOf<T>::value();
+    cx[j] = Pair<T>{T(0), T(0)};
+  }
+  for (int k0 = 0; k0 < W; k0 += KB) {
+    if (k0 > 0) {
+#pragma unroll
+      for (int i = 0; i < KB; ++i) {
+        if (k0 + i < W) {
+          o[i] = offs[k0 + i];
+          c[i] = planes.cvals[k0 + i];
+        }
+      }
+    }
+    T xv[NWIN][R][KB][2];
+#pragma unroll
+    for (int i = 0; i < KB; ++i) {
+      if (k0 + i < W) {
+        const DiaSrc src = Run::src(P, i);
+#pragma unroll
+        for (int w = 0; w < NWIN; ++w) {
+          // block-uniform address of the block's first column
+          const T* ub = own[w] + (cb + o[i]);
+          const bool aligned =
+              src == kDiaLoadAligned ||
+              (reinterpret_cast<uintptr_t>(ub) % sizeof(Pair<T>)) == 0;
+#pragma unroll
+          for (int j = 0; j < R; ++j) {
+            const T* p = ub + t2 + j * 2 * BLK;
+            if (src == kDiaFromHi) {
+              // element 0 of the first lane; p[3] is element 1 of diagonal
+              // i + 2's pair, which the last lane lacks
+              if (lane == 0 || (Run::two(P, i) && lane == 63)) {
+                xv[w][j][i][0] = p[lane == 0 ? 0 : 3];
+              }
+            } else if (src == kDiaFromLo) {
+              if (!(i >= 2 && Run::two(P, i - 2)) && lane == 63) {
+                xv[w][j][i][0] = p[1];
+              }
+            } else if (aligned) {
+              const Pair<T> t = *reinterpret_cast<const Pair<T>*>(p);
+              xv[w][j][i][0] = t.a;
+              xv[w][j][i][1] = t.b;
+            } else {
+              xv[w][j][i][0] = p[0];
+              xv[w][j][i][1] = p[1];
+            }
+          }
+        }
+      }
+    }
+    if (k0 == 0) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) pre(j, rb + t2 + j * 2 * BLK, true, ctr);
+      // keep the scheduler from sinking loads below the first use
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (ADJ != 0 && P >= 0) {
+      // borrowed pairs; their neighbours are loaded pairs and stay as they are
+#pragma unroll
+      for (int w = 0; w < NWIN; ++w) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          T edge[KB];  // what the one- or two-lane load of diagonal i brought
+#pragma unroll
+          for (int i = 0; i < KB; ++i) {
+            edge[i] = xv[w][j][i][0];
+            if (Run::src(P, i) == kDiaFromLo) {
+              const bool shared = i >= 2 && Run::two(P, i - 2);
+              const T e = shared ? edge[i >= 2 ? i - 2 : 0] : edge[i];
+              const T up = lane_above(xv[w][j][i > 0 ? i - 1 : 0][0]);
+              xv[w][j][i][0] = xv[w][j][i > 0 ? i - 1 : 0][1];
+              xv[w][j][i][1] = lane == 63 ? e : up;
+            } else if (Run::src(P, i) == kDiaFromHi) {
+              const T dn = lane_below(xv[w][j][i + 1 < KB ? i + 1 : i][1]);
+              xv[w][j][i][1] = xv[w][j][i + 1 < KB ? i + 1 : i][0];
+              xv[w][j][i][0] = lane == 0 ? edge[i] : dn;
+            }
+          }
+        }
+      }
+    }
+    if (WC > 0 && ctr) {
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        cx[j] = Pair<T>{xv[0][j][(KB - 1) / 2][0], xv[0][j][(KB - 1) / 2][1]};
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+      const uint32_t m0 = (uint32_t)(M)mw[j];
+      const uint32_t m1 = (uint32_t)(mw[j] >> (8 * sizeof(M)));
+#pragma unroll
+      for (int i = 0; i < KB; ++i) {
+        if (k0 + i < W) {
+          T v0[NWIN], v1[NWIN];
+#pragma unroll
+          for (int w = 0; w < NWIN; ++w) {
+            v0[w] = xv[w][j][i][0];
+            v1[w] = xv[w][j][i][1];
+          }
+          const uint32_t bit = 1u << (k0 + i);
+          a[j][0] = fmadd((m0 & bit) ? c[i] : T(0), comb(v0), a[j][0]);
+          a[j][1] = fmadd((m1 & bit) ? c[i] : T(0), comb(v1), a[j][1]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    post(j, rb + t2 + j * 2 * BLK, a[j][0], a[j][1], true, ctr, cx[j]);
+  }
+}
 
 // offs must be ascending (build_dia: torch.unique).  win0 and (NWIN == 2)
-// win1 share one geometry; comb(v) folds the NWIN loaded values of a column into its x.
-// pre(j, r0, full) issues the caller's operand loads of pair j and
-// post(j, r0, a0, a1, full) consumes its sums; full = rows r0, r0+1 are both
-// below min(m, rhi).  Edge blocks skip pairs with r0 >= rhi.
-template <int WC, int R, bool SINGLE, int NWIN, typename T, typename M,
-          typename Comb, typename Pre, typename Post>
+// win1 share one geometry; comb(v) folds the NWIN loaded values of a column
+// into its x.  pre(j, r0, full, ctr) issues the caller's operand loads of
+// pair j and post(j, r0, a0, a1, full, ctr, cx) consumes its sums; full =
+// rows r0, r0+1 are both below min(m, rhi).  Edge blocks skip pairs with
+// r0 >= rhi.
+// rowvec (or null) is an operand the caller reads at rows r0, r0+1.  Where
+// it is the own x slab at the rows' own columns (CG's p in p . A p, the
+// Jacobi iterate) and the middle diagonal of a compile-time W has offset 0,
+// an interior block sets ctr: pre must then not load that operand, and post
+// finds its pair in cx, the offset-0 pair the core holds anyway.
+template <int WC, int R, bool SINGLE, int NWIN, uint32_t ADJ, typename T,
+          typename M, typename Comb, typename Pre, typename Post>
 __device__ __forceinline__ void dia_const_rows(
     const DiaConstPlanes<T, M>& planes, const int64_t* __restrict__ offs,
     int Wrt, const XWindow<T>& win0, const XWindow<T>& win1, Comb comb,
-    int64_t m, int64_t row0, int64_t col_lo, int64_t rbase, int64_t rhi,
-    Pre pre, Post post) {
+    const T* rowvec, int64_t m, int64_t row0, int64_t col_lo, int64_t rbase,
+    int64_t rhi, Pre pre, Post post) {
   constexpr int KB = WC ? WC : 8;  // diagonals per load batch
   constexpr int64_t S = 2 * (int64_t)BLK * R;
+  static_assert(ADJ == 0 || (WC > 0 && (ADJ >> (KB - 1)) == 0),
+                "a plan needs a compile-time W");
+  using Run = DiaRun<ADJ>;
   const int W = WC ? WC : Wrt;
   const int64_t lim = min(m, rhi);
   const int64_t rb = rbase + (int64_t)blockIdx.x * S;
-  const int64_t t2 = 2 * (int64_t)threadIdx.x;
   // own-piece index of row rb's main-diagonal column
   const int64_t cb = row0 + rb - col_lo - win0.nlo;
   const int64_t own_end = min(win0.nown, win0.wsize - win0.nlo);
@@ -851,91 +1075,45 @@ __device__ __forceinline__ void dia_const_rows(
       c[i] = planes.cvals[i];
     }
   }
-  const bool interior = rb + S <= lim && cb + o[0] >= 0 &&
-                        cb + (S - 1) + (WC ? o[KB - 1] : offs[W - 1]) < own_end;
+  bool interior = rb + S <= lim && cb + o[0] >= 0 &&
+                  cb + (S - 1) + (WC ? o[KB - 1] : offs[W - 1]) < own_end;
+#pragma unroll
+  for (int q = 1; q < Run::len; ++q) {
+    interior = interior && o[Run::start + q] == o[Run::start] + q;
+  }
   if (interior) {
-    using M2 = typename UIntOf<2 * sizeof(M)>::type;
-    M2 mw[R];
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      mw[j] = nt_load(
-          reinterpret_cast<const M2*>(planes.mask + rb + t2 + j * 2 * BLK));
-    }
-    T a[R][2];
-#pragma unroll
-    for (int j = 0; j < R; ++j) a[j][0] = a[j][1] = ZeroOf<T>::value();
-    for (int k0 = 0; k0 < W; k0 += KB) {
-      if (k0 > 0) {
-#pragma unroll
-        for (int i = 0; i < KB; ++i) {
-          if (k0 + i < W) {
-            o[i] = offs[k0 + i];
-            c[i] = planes.cvals[k0 + i];
-          }
-        }
+    const T* own[NWIN];
+    own[0] = win0.own;
+    own[NWIN - 1] = (NWIN == 2 ? win1 : win0).own;
+    const bool ctr = WC > 0 && NWIN == 1 && rowvec != nullptr &&
+                     rowvec + rb == win0.own + cb && o[(KB - 1) / 2] == 0;
+    auto body = [&](auto par) {
+      dia_const_interior<WC, R, NWIN, ADJ, decltype(par)::value>(
+          planes, offs, W, own, comb, ctr, rb, cb, o, c, pre, post);
+    };
+    if (ADJ == 0) {
+      body(std::integral_constant<int, -1>{});
+    } else {
+      const T* u0 = own[0] + (cb + o[Run::start]);
+      const T* u1 = own[NWIN - 1] + (cb + o[Run::start]);
+      const bool un0 = reinterpret_cast<uintptr_t>(u0) % sizeof(Pair<T>) != 0;
+      const bool un1 = reinterpret_cast<uintptr_t>(u1) % sizeof(Pair<T>) != 0;
+      if (un0 != un1) {
+        body(std::integral_constant<int, -1>{});
+      } else if (un0) {
+        body(std::integral_constant<int, 1>{});
+      } else {
+        body(std::integral_constant<int, 0>{});
       }
-      T xv[NWIN][R][KB][2];
-#pragma unroll
-      for (int i = 0; i < KB; ++i) {
-        if (k0 + i < W) {
-#pragma unroll
-          for (int w = 0; w < NWIN; ++w) {
-            // block-uniform address of the block's first column
-            const T* ub = (w == 0 ? win0 : win1).own + (cb + o[i]);
-            const bool aligned =
-                (reinterpret_cast<uintptr_t>(ub) % sizeof(Pair<T>)) == 0;
-#pragma unroll
-            for (int j = 0; j < R; ++j) {
-              const T* p = ub + t2 + j * 2 * BLK;
-              if (aligned) {
-                const Pair<T> t = *reinterpret_cast<const Pair<T>*>(p);
-                xv[w][j][i][0] = t.a;
-                xv[w][j][i][1] = t.b;
-              } else {
-                xv[w][j][i][0] = p[0];
-                xv[w][j][i][1] = p[1];
-              }
-            }
-          }
-        }
-      }
-      if (k0 == 0) {
-#pragma unroll
-        for (int j = 0; j < R; ++j) pre(j, rb + t2 + j * 2 * BLK, true);
-        // keep the scheduler from sinking loads below the first use
-        __builtin_amdgcn_sched_barrier(0);
-      }
-#pragma unroll
-      for (int j = 0; j < R; ++j) {
-        const uint32_t m0 = (uint32_t)(M)mw[j];
-        const uint32_t m1 = (uint32_t)(mw[j] >> (8 * sizeof(M)));
-#pragma unroll
-        for (int i = 0; i < KB; ++i) {
-          if (k0 + i < W) {
-            T v0[NWIN], v1[NWIN];
-#pragma unroll
-            for (int w = 0; w < NWIN; ++w) {
-              v0[w] = xv[w][j][i][0];
-              v1[w] = xv[w][j][i][1];
-            }
-            const uint32_t bit = 1u << (k0 + i);
-            a[j][0] = fmadd((m0 & bit) ? c[i] : T(0), comb(v0), a[j][0]);
-            a[j][1] = fmadd((m1 & bit) ? c[i] : T(0), comb(v1), a[j][1]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < R; ++j) {
-      post(j, rb + t2 + j * 2 * BLK, a[j][0], a[j][1], true);
     }
   } else {
+    const int64_t t2 = 2 * (int64_t)threadIdx.x;
 #pragma unroll
     for (int j = 0; j < R; ++j) {
       const int64_t r0 = rb + t2 + j * 2 * BLK;
       if (r0 < rhi) {
         T a0 = ZeroOf<T>::value(), a1 = ZeroOf<T>::value();
-        pre(j, r0, r0 + 1 < lim);
+        pre(j, r0, r0 + 1 < lim, false);
         dia_accumulate(
             planes, offs, W, r0, row0 + r0 - col_lo,
             [&](int64_t c0, T& x0, T& x1) {
@@ -949,20 +1127,20 @@ __device__ __forceinline__ void dia_const_rows(
               x1 = comb(v1);
             },
             a0, a1);
-        post(j, r0, a0, a1, r0 + 1 < lim);
+        post(j, r0, a0, a1, r0 + 1 < lim, false, Pair<T>{T(0), T(0)});
       }
     }
   }
 }
 
-template <typename T, typename M, int WC, bool FUSE_DOT, bool SINGLE,
-          bool RESID>
+template <typename T, typename M, int WC, uint32_t ADJ, bool FUSE_DOT,
+          bool SINGLE, bool RESID>
 __global__ __launch_bounds__(BLK) void dia_const_spmv_kernel(
     const DiaConstPlanes<T, M> planes, const int64_t* __restrict__ offs,
     const XWindow<T> win, T* __restrict__ y, const T* __restrict__ pvec,
     T* __restrict__ dot_partial, int64_t m, int W, int64_t col_lo,
     int64_t row0, int64_t rbase, int64_t rhi) {
-  constexpr int R = kDiaPairs;
+  constexpr int R = dia_spmv_pairs(WC, RESID);
   const int64_t lim = min(m, rhi);
   Pair<T> pv[R];  // p (FUSE_DOT) or b (RESID) of the pair's rows
   T d[R];
@@ -971,11 +1149,11 @@ __global__ __launch_bounds__(BLK) void dia_const_spmv_kernel(
     pv[j] = Pair<T>{T(0), T(0)};
     d[j] = T(0);
   }
-  dia_const_rows<WC, R, SINGLE, 1>(
-      planes, offs, W, win, win, [](const T(&v)[1]) { return v[0]; }, m,
-      row0, col_lo, rbase, rhi,
-      [&](int j, int64_t r0, bool full) {
-        if (FUSE_DOT || RESID) {
+  dia_const_rows<WC, R, SINGLE, 1, ADJ>(
+      planes, offs, W, win, win, [](const T(&v)[1]) { return v[0]; },
+      (FUSE_DOT || RESID) ? pvec : nullptr, m, row0, col_lo, rbase, rhi,
+      [&](int j, int64_t r0, bool full, bool ctr) {
+        if ((FUSE_DOT || RESID) && !ctr) {
           if (full) {
             pv[j] = *reinterpret_cast<const Pair<T>*>(&pvec[r0]);
           } else if (r0 < lim) {
@@ -983,7 +1161,8 @@ __global__ __launch_bounds__(BLK) void dia_const_spmv_kernel(
           }
         }
       },
-      [&](int j, int64_t r0, T a0, T a1, bool full) {
+      [&](int j, int64_t r0, T a0, T a1, bool full, bool ctr, Pair<T> cx) {
+        if (ctr) pv[j] = cx;
         if (RESID) {
           // y = b - A x: the V-cycle residual fused into the SpMV
           a0 = pv[j].a - a0;
@@ -1010,26 +1189,27 @@ __global__ __launch_bounds__(BLK) void dia_const_spmv_kernel(
   }
 }
 
-template <typename T, typename M, int WC, bool SINGLE>
+template <typename T, typename M, int WC, uint32_t ADJ, bool SINGLE>
 __global__ __launch_bounds__(BLK) void dia_const_jacobi_kernel(
     const DiaConstPlanes<T, M> planes, const int64_t* __restrict__ offs,
     const XWindow<T> win, const T* __restrict__ xloc,
     const T* __restrict__ b, const T* __restrict__ dinv,
     T* __restrict__ xout, int64_t m, int W, int64_t col_lo, int64_t row0,
     T omega, int64_t rbase, int64_t rhi) {
-  constexpr int R = kDiaPairs;
+  constexpr int R = kDiaSmoothPairs;
   Pair<T> xv[R], bv[R], dv[R];
-  dia_const_rows<WC, R, SINGLE, 1>(
-      planes, offs, W, win, win, [](const T(&v)[1]) { return v[0]; }, m,
-      row0, col_lo, rbase, rhi,
-      [&](int j, int64_t r0, bool full) {
+  dia_const_rows<WC, R, SINGLE, 1, ADJ>(
+      planes, offs, W, win, win, [](const T(&v)[1]) { return v[0]; }, xloc,
+      m, row0, col_lo, rbase, rhi,
+      [&](int j, int64_t r0, bool full, bool ctr) {
         if (full) {
-          xv[j] = *reinterpret_cast<const Pair<T>*>(&xloc[r0]);
+          if (!ctr) xv[j] = *reinterpret_cast<const Pair<T>*>(&xloc[r0]);
           bv[j] = *reinterpret_cast<const Pair<T>*>(&b[r0]);
           dv[j] = *reinterpret_cast<const Pair<T>*>(&dinv[r0]);
         }
       },
-      [&](int j, int64_t r0, T a0, T a1, bool full) {
+      [&](int j, int64_t r0, T a0, T a1, bool full, bool ctr, Pair<T> cx) {
+        if (ctr) xv[j] = cx;
         if (full) {
           *reinterpret_cast<Pair<T>*>(&xout[r0]) =
               Pair<T>{fmadd(omega * dv[j].a, bv[j].a - a0, xv[j].a),
@@ -1041,7 +1221,7 @@ __global__ __launch_bounds__(BLK) void dia_const_jacobi_kernel(
 }
 
 // dia_spmv_bpdot_kernel on the constant-plane source
-template <typename T, typename M, int WC, bool SINGLE>
+template <typename T, typename M, int WC, uint32_t ADJ, bool SINGLE>
 __global__ __launch_bounds__(BLK) void dia_const_bpdot_kernel(
     const DiaConstPlanes<T, M> planes, const int64_t* __restrict__ offs,
     const XWindow<T> rwin, const XWindow<T> pwin, T* __restrict__ pnew,
@@ -1055,16 +1235,17 @@ __global__ __launch_bounds__(BLK) void dia_const_bpdot_kernel(
   T d[R];
 #pragma unroll
   for (int j = 0; j < R; ++j) d[j] = T(0);
-  dia_const_rows<WC, R, SINGLE, 2>(
-      planes, offs, W, rwin, pwin, comb, m, row0, col_lo, 0, mp,
-      [&](int j, int64_t r0, bool) {
+  dia_const_rows<WC, R, SINGLE, 2, ADJ>(
+      planes, offs, W, rwin, pwin, comb, (const T*)nullptr, m, row0, col_lo,
+      0, mp,
+      [&](int j, int64_t r0, bool, bool) {
         // clamped like the streamed kernel's: offset 0 need not be a
         // diagonal, and row r0 + 1 of a lone tail is loaded but never used
         const int64_t c0 = row0 + r0 - col_lo;
         rwin.template pair<SINGLE, true>(c0, rr[j][0], rr[j][1]);
         pwin.template pair<SINGLE, true>(c0, pp[j][0], pp[j][1]);
       },
-      [&](int j, int64_t r0, T a0, T a1, bool full) {
+      [&](int j, int64_t r0, T a0, T a1, bool full, bool, Pair<T>) {
         // own-row p_new: the formula of the window recompute, same bits
         const T v0[2] = {rr[j][0], pp[j][0]}, v1[2] = {rr[j][1], pp[j][1]};
         const T p0 = comb(v0), p1 = comb(v1);
@@ -1186,22 +1367,48 @@ struct DiaConstOf<DiaConstPlanes<T, M>> : std::true_type {
   using mask_t = M;
 };
 
-// f(integral_constant WC) for the constant-plane kernels: W itself under a
-// u8 mask (1 <= W <= 8), 0 (run-time W) under the wider masks
+// The lane-exchange plans a compile-time W = N is built for, chosen from the
+// mirror's adjacency word (bit i: offs[i + 1] == offs[i] + 1): the whole
+// band (tridiagonal, pentadiagonal, ...), else the three middle diagonals
+// of an odd W >= 5 (the -1, 0, +1 of a 5-pt or 7-pt stencil), else none.
+// Any other adjacency loads every pair, which is always correct.
+template <int N, typename F>
+void dispatch_dia_adj(int64_t adj, F&& f) {
+  constexpr uint32_t band = (1u << (N - 1)) - 1;
+  constexpr uint32_t mid = (N % 2 == 1 && N >= 5) ? 3u << (N / 2 - 1) : 0;
+  const std::integral_constant<int, N> wc;
+  if constexpr (band != 0) {
+    if ((adj & band) == band) {
+      f(wc, std::integral_constant<uint32_t, band>{});
+      return;
+    }
+  }
+  if constexpr (mid != 0) {
+    if ((adj & mid) == mid) {
+      f(wc, std::integral_constant<uint32_t, mid>{});
+      return;
+    }
+  }
+  f(wc, std::integral_constant<uint32_t, 0>{});
+}
+
+// f(integral_constant WC, integral_constant ADJ) for the constant-plane
+// kernels: W itself under a u8 mask (1 <= W <= 8) with its lane-exchange
+// plan, 0 (run-time W, no plan) under the wider masks
 template <typename M, typename F>
-void dispatch_dia_wc(int64_t W, F&& f) {
+void dispatch_dia_wc(int64_t W, int64_t adj, F&& f) {
   TORCH_CHECK(W >= 1, "dia: at least one diagonal expected");
   if constexpr (std::is_same_v<M, uint8_t>) {
     switch (W) {
 #define SPARSE_DIA_WC(N) \
-  case N: f(std::integral_constant<int, N>{}); return;
+  case N: dispatch_dia_adj<N>(adj, f); return;
       SPARSE_DIA_WC(1) SPARSE_DIA_WC(2) SPARSE_DIA_WC(3) SPARSE_DIA_WC(4)
       SPARSE_DIA_WC(5) SPARSE_DIA_WC(6) SPARSE_DIA_WC(7) SPARSE_DIA_WC(8)
 #undef SPARSE_DIA_WC
       default: break;
     }
   }
-  f(std::integral_constant<int, 0>{});
+  f(std::integral_constant<int, 0>{}, std::integral_constant<uint32_t, 0>{});
 }
 
 }  // namespace
@@ -1368,7 +1575,7 @@ static at::Tensor dia_spmv_impl(const at::Tensor& planes, const OptTensor& mask,
                                 at::Tensor& y, const at::Tensor* pvec,
                                 int64_t W, int64_t m, int64_t col_lo,
                                 int64_t row0, int64_t wsize, int64_t rbase,
-                                int64_t rhi) {
+                                int64_t rhi, int64_t adj) {
   const RowPairLaunch L(dia_mp(planes, mask, W), hlo, own, hhi, wsize, rbase,
                         rhi);
   const bool fuse_dot = pvec && !RESID;
@@ -1386,9 +1593,10 @@ static at::Tensor dia_spmv_impl(const at::Tensor& planes, const OptTensor& mask,
           if constexpr (RESID && decltype(fuse)::value) {
           } else if constexpr (DiaConstOf<PL>::value) {
             using M = typename DiaConstOf<PL>::mask_t;
-            dispatch_dia_wc<M>(W, [&](auto wc) {
-              L.launch_pairs<kDiaPairs>(
+            dispatch_dia_wc<M>(W, adj, [&](auto wc, auto plan) {
+              L.launch_pairs<dia_spmv_pairs(decltype(wc)::value, RESID)>(
                   dia_const_spmv_kernel<T, M, decltype(wc)::value,
+                                        decltype(plan)::value,
                                         decltype(fuse)::value,
                                         decltype(single)::value, RESID>,
                   pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
@@ -1413,19 +1621,20 @@ void dia_spmv_plain_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
                         at::Tensor hlo, at::Tensor own, at::Tensor hhi,
                         at::Tensor y, int64_t W, int64_t m, int64_t col_lo,
                         int64_t row0, int64_t wsize, int64_t rbase,
-                        int64_t rhi) {
+                        int64_t rhi, int64_t adj) {
   dia_spmv_impl<false>(planes, mask, offs, hlo, own, hhi, y, nullptr, W, m,
-                       col_lo, row0, wsize, rbase, rhi);
+                       col_lo, row0, wsize, rbase, rhi, adj);
 }
 
 at::Tensor dia_spmv_dot_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
                             at::Tensor hlo, at::Tensor own, at::Tensor hhi,
                             at::Tensor y, at::Tensor pvec, int64_t W,
                             int64_t m, int64_t col_lo, int64_t row0,
-                            int64_t wsize, int64_t rbase, int64_t rhi) {
+                            int64_t wsize, int64_t rbase, int64_t rhi,
+                            int64_t adj) {
   return sum_or_zero(dia_spmv_impl<false>(planes, mask, offs, hlo, own, hhi, y,
                                           &pvec, W, m, col_lo, row0, wsize,
-                                          rbase, rhi),
+                                          rbase, rhi, adj),
                      planes);
 }
 
@@ -1433,9 +1642,9 @@ void dia_residual_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
                       at::Tensor hlo, at::Tensor own, at::Tensor hhi,
                       at::Tensor b, at::Tensor y, int64_t W, int64_t m,
                       int64_t col_lo, int64_t row0, int64_t wsize,
-                      int64_t rbase, int64_t rhi) {
+                      int64_t rbase, int64_t rhi, int64_t adj) {
   dia_spmv_impl<true>(planes, mask, offs, hlo, own, hhi, y, &b, W, m, col_lo,
-                      row0, wsize, rbase, rhi);
+                      row0, wsize, rbase, rhi, adj);
 }
 
 void dia_jacobi_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
@@ -1443,7 +1652,7 @@ void dia_jacobi_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
                     at::Tensor xloc, at::Tensor b, at::Tensor dinv,
                     at::Tensor xout, int64_t W, int64_t m, int64_t col_lo,
                     int64_t row0, int64_t wsize, double omega, int64_t rbase,
-                    int64_t rhi) {
+                    int64_t rhi, int64_t adj) {
   const RowPairLaunch L(dia_mp(planes, mask, W), hlo, own, hhi, wsize, rbase,
                         rhi);
   if (L.empty()) return;
@@ -1454,9 +1663,10 @@ void dia_jacobi_hip(at::Tensor planes, OptTensor mask, at::Tensor offs,
         using PL = decltype(pl);
         if constexpr (DiaConstOf<PL>::value) {
           using M = typename DiaConstOf<PL>::mask_t;
-          dispatch_dia_wc<M>(W, [&](auto wc) {
-            L.launch_pairs<kDiaPairs>(
+          dispatch_dia_wc<M>(W, adj, [&](auto wc, auto plan) {
+            L.launch_pairs<kDiaSmoothPairs>(
                 dia_const_jacobi_kernel<T, M, decltype(wc)::value,
+                                        decltype(plan)::value,
                                         decltype(single)::value>,
                 pl, offs.data_ptr<int64_t>(), L.window<T>(hlo, own, hhi),
                 xloc.data_ptr<T>(), b.data_ptr<T>(), dinv.data_ptr<T>(),
@@ -1482,7 +1692,7 @@ at::Tensor dia_spmv_bpdot_hip(at::Tensor planes, OptTensor mask,
                               at::Tensor p_hhi, at::Tensor pnew, at::Tensor q,
                               at::Tensor beta_num, at::Tensor beta_den,
                               int64_t W, int64_t m, int64_t col_lo,
-                              int64_t row0, int64_t wsize) {
+                              int64_t row0, int64_t wsize, int64_t adj) {
   TORCH_CHECK(pnew.data_ptr() != p_own.data_ptr(),
               "dia_spmv_bpdot: pnew must not alias p_own (double-buffer)");
   const RowPairLaunch L(dia_mp(planes, mask, W), r_hlo, r_own, r_hhi, wsize);
@@ -1504,9 +1714,10 @@ at::Tensor dia_spmv_bpdot_hip(at::Tensor planes, OptTensor mask,
         };
         if constexpr (DiaConstOf<PL>::value) {
           using M = typename DiaConstOf<PL>::mask_t;
-          dispatch_dia_wc<M>(W, [&](auto wc) {
+          dispatch_dia_wc<M>(W, adj, [&](auto wc, auto plan) {
             go([&](auto... a) { L.launch_pairs<kDiaBpdotPairs>(a...); },
                dia_const_bpdot_kernel<T, M, decltype(wc)::value,
+                                      decltype(plan)::value,
                                       decltype(single)::value>);
           });
         } else {
