@@ -377,10 +377,14 @@ def _spgemm_esc(A, B, a_col_lo, vdt):
     return LocalCSR(indptr, cols, out_vals, A.nrows, B.ncols)
 
 
-def axpby(y, x, a, b, isalpha: bool, negate: bool):
+def axpby(y, x, a, b, isalpha: bool, negate: bool, *, nt: int = -1):
     """Fused y = y + (±a/b) x  (isalpha) or y = x + (±a/b) y.
-    Reference: AXPBY task (axpby.cu:25-42, linalg.py:479-496)."""
-    ext().axpby(y, x, a, b, bool(isalpha), bool(negate))
+    Reference: AXPBY task (axpby.cu:25-42, linalg.py:479-496).
+    nt: 0 plain memory accesses, 1 non-temporal loads of x, 2 non-temporal
+    loads and stores; -1 (default) lets the kernel choose by vector length.
+    The result is the same bits in every mode; complex dtypes always take the
+    plain accesses."""
+    ext().axpby(y, x, a, b, bool(isalpha), bool(negate), int(nt))
 
 
 def rk_calc_dy(K, a, h, dy):
@@ -565,16 +569,17 @@ def dia_spmv_bpdot(dm: DiaMirror, r_pieces, p_pieces, pnew, q,
                                 int(wsize), dm.adj)
 
 
-def cg_xr_norm2(x, p, r, q, a, b):
+def cg_xr_norm2(x, p, r, q, a, b, *, nt: int = -1):
     """Fused CG K2: x += (a/b)p; r -= (a/b)q; returns local sum(r_new^2)
-    as a device 0-dim tensor."""
+    as a device 0-dim tensor.  nt as in axpby (1: loads of p and q)."""
     n = x.numel()
     if n == 0:
         return torch.zeros((), dtype=x.dtype, device=x.device)
     ept = max(1, 16 // x.element_size())
     blocks = (n // ept + 255) // 256 + 1
     partial = torch.empty(blocks, dtype=x.dtype, device=x.device)
-    ext().cg_xr_norm2(x, p, r, q, a.to(x.dtype), b.to(x.dtype), partial)
+    ext().cg_xr_norm2(x, p, r, q, a.to(x.dtype), b.to(x.dtype), partial,
+                      int(nt))
     return partial.sum()
 
 

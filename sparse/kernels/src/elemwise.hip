@@ -117,6 +117,13 @@ __global__ void mult_dense_kernel(const int64_t* __restrict__ indptr,
 // 4 for fp32, 2 for fp64; 8B accesses run at ~0.6x the 16B rate on
 // gfx950).  Flat (no grid-stride loop): measured 5865 vs 5070 GB/s for
 // the strided form at 268M fp64 (tools/axpby_bench.hip).
+// One chunk of 256 vectors per block, and the scalar preamble (*a, *b, the
+// divide) ahead of the loads as hipcc orders it: measured at 268M and 36M
+// fp64 (tools/stream_bench.hip, profiles/stream_core_bench.txt), issuing the
+// loads first changes nothing, nor does handing s in by value, and 2, 4 or 8
+// chunks per block are 1-11 % SLOWER.  These kernels are not held up by their
+// preamble.  What does move them is the cache policy of the accesses: see
+// stream_nt_mode below.
 template <typename T>
 struct EptOf {
   static constexpr int value =
@@ -130,7 +137,42 @@ struct alignas(EptOf<T>::value * sizeof(T) <= 16
   T v[EptOf<T>::value];
 };
 
-template <typename T, bool ISALPHA, bool NEG>
+// The 16-byte vector access of the streaming kernels, plain or non-temporal.
+// Non-temporal pays only on vectors too long for the Infinity Cache to hold
+// (stream_nt_mode below); the bits moved are the same either way.
+typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
+
+template <bool NT, typename T>
+__device__ __forceinline__ VVec<T> vec_load(const VVec<T>* p) {
+  if constexpr (NT) {
+    static_assert(sizeof(VVec<T>) == 16, "non-temporal path moves 16 bytes");
+    const u32x4_t t =
+        __builtin_nontemporal_load(reinterpret_cast<const u32x4_t*>(p));
+    VVec<T> v;
+    __builtin_memcpy(&v, &t, 16);
+    return v;
+  } else {
+    return *p;
+  }
+}
+
+template <bool NT, typename T>
+__device__ __forceinline__ void vec_store(VVec<T>* p, const VVec<T>& v) {
+  if constexpr (NT) {
+    static_assert(sizeof(VVec<T>) == 16, "non-temporal path moves 16 bytes");
+    u32x4_t t;
+    __builtin_memcpy(&t, &v, 16);
+    __builtin_nontemporal_store(t, reinterpret_cast<u32x4_t*>(p));
+  } else {
+    *p = v;
+  }
+}
+
+// What a streaming kernel marks non-temporal: nothing, the loads of the
+// streams it only reads, or every vector load and store.
+enum : int { NT_NONE = 0, NT_READS = 1, NT_ALL = 2 };
+
+template <typename T, bool ISALPHA, bool NEG, int NT>
 __global__ __launch_bounds__(256) void axpby_kernel(
     T* __restrict__ y, const T* __restrict__ x, const T* __restrict__ a,
     const T* __restrict__ b, int64_t n) {
@@ -142,19 +184,35 @@ __global__ __launch_bounds__(256) void axpby_kernel(
   if (i < nv) {
     auto* y2 = reinterpret_cast<VVec<T>*>(y);
     auto* x2 = reinterpret_cast<const VVec<T>*>(x);
-    VVec<T> yv = y2[i];
-    const VVec<T> xv = x2[i];
+    VVec<T> yv = vec_load<NT == NT_ALL>(y2 + i);
+    const VVec<T> xv = vec_load<NT != NT_NONE>(x2 + i);
 #pragma unroll
     for (int j = 0; j < EPT; ++j) {
       yv.v[j] = ISALPHA ? (yv.v[j] + s * xv.v[j]) : (xv.v[j] + s * yv.v[j]);
     }
-    y2[i] = yv;
+    vec_store<NT == NT_ALL>(y2 + i, yv);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     for (int64_t t = nv * EPT; t < n; ++t) {
       y[t] = ISALPHA ? (y[t] + s * x[t]) : (x[t] + s * y[t]);
     }
   }
+}
+
+// The `nt` argument of the streaming ops: 0, 1, 2 force NT_NONE, NT_READS,
+// NT_ALL; -1 takes the measured choice.  A vector that alone fills the
+// 256 MiB Infinity Cache cannot be found there by the next kernel, and there
+// the non-temporal form streams 4-9 % faster (fp64, 288 MB and 2.1 GB per
+// vector).  At 64 MB and 8 MB per vector it is 5-10 % slower, so shorter
+// vectors (the multigrid levels, the Krylov solvers' usual sizes) stay plain
+// (profiles/stream_core_bench.txt).
+constexpr int kStreamNtAuto = NT_ALL;
+constexpr int64_t kStreamNtMinBytes = int64_t(256) << 20;
+
+inline int stream_nt_mode(int64_t nt, int64_t vec_bytes, const char* who) {
+  TORCH_CHECK(nt >= -1 && nt <= 2, who, ": nt must be -1, 0, 1 or 2, got ", nt);
+  if (nt >= 0) return (int)nt;
+  return vec_bytes >= kStreamNtMinBytes ? kStreamNtAuto : NT_NONE;
 }
 
 }  // namespace
@@ -243,8 +301,9 @@ void mult_dense_hip(at::Tensor indptr, at::Tensor indices, at::Tensor vals,
 }
 
 void axpby_hip(at::Tensor y, at::Tensor x, at::Tensor a, at::Tensor b,
-               bool isalpha, bool negate) {
+               bool isalpha, bool negate, int64_t nt) {
   int64_t n = y.numel();
+  const int mode = stream_nt_mode(nt, n * y.element_size(), "axpby");
   if (n == 0) return;
   const int64_t ept = std::max<int64_t>(1, 16 / y.element_size());
   int64_t blocks = (n / ept + 255) / 256 + 1;
@@ -255,10 +314,20 @@ void axpby_hip(at::Tensor y, at::Tensor x, at::Tensor a, at::Tensor b,
                          y.data_ptr<T>(), x.data_ptr<T>(), a.data_ptr<T>(),
                          b.data_ptr<T>(), n);
     };
-    if (isalpha && !negate) launch(axpby_kernel<T, true, false>);
-    else if (isalpha && negate) launch(axpby_kernel<T, true, true>);
-    else if (!isalpha && !negate) launch(axpby_kernel<T, false, false>);
-    else launch(axpby_kernel<T, false, true>);
+    auto form = [&](auto ntc) {
+      // Complex stays plain in every mode: behind a non-temporal load hipcc
+      // fuses the other product of a complex multiply-add, and the last bit
+      // of the result would depend on the mode.
+      constexpr int NT =
+          c10::is_complex<T>::value ? (int)NT_NONE : decltype(ntc)::value;
+      if (isalpha && !negate) launch(axpby_kernel<T, true, false, NT>);
+      else if (isalpha && negate) launch(axpby_kernel<T, true, true, NT>);
+      else if (!isalpha && !negate) launch(axpby_kernel<T, false, false, NT>);
+      else launch(axpby_kernel<T, false, true, NT>);
+    };
+    if (mode == NT_ALL) form(std::integral_constant<int, NT_ALL>{});
+    else if (mode == NT_READS) form(std::integral_constant<int, NT_READS>{});
+    else form(std::integral_constant<int, NT_NONE>{});
   });
 }
 
@@ -304,7 +373,7 @@ __global__ __launch_bounds__(256) void axpby_norm2_kernel(
 // One pass over 4 streams (reads x,p,r,q; writes x,r) instead of the
 // separate x-axpby + r-axpby_norm2 pair — saves 2 full HBM passes per CG
 // iteration at n=268M.
-template <typename T>
+template <typename T, int NT>
 __global__ __launch_bounds__(256) void cg_xr_norm2_kernel(
     T* __restrict__ x, const T* __restrict__ p, T* __restrict__ r,
     const T* __restrict__ q, const T* __restrict__ a, const T* __restrict__ b,
@@ -319,18 +388,18 @@ __global__ __launch_bounds__(256) void cg_xr_norm2_kernel(
     auto* r2 = reinterpret_cast<VVec<T>*>(r);
     auto* p2 = reinterpret_cast<const VVec<T>*>(p);
     auto* q2 = reinterpret_cast<const VVec<T>*>(q);
-    VVec<T> xv = x2[i];
-    VVec<T> rv = r2[i];
-    const VVec<T> pv = p2[i];
-    const VVec<T> qv = q2[i];
+    VVec<T> xv = vec_load<NT == NT_ALL>(x2 + i);
+    VVec<T> rv = vec_load<NT == NT_ALL>(r2 + i);
+    const VVec<T> pv = vec_load<NT != NT_NONE>(p2 + i);
+    const VVec<T> qv = vec_load<NT != NT_NONE>(q2 + i);
 #pragma unroll
     for (int j = 0; j < EPT; ++j) {
       xv.v[j] += s * pv.v[j];
       rv.v[j] -= s * qv.v[j];
       acc += rv.v[j] * rv.v[j];
     }
-    x2[i] = xv;
-    r2[i] = rv;
+    vec_store<NT == NT_ALL>(x2 + i, xv);
+    vec_store<NT == NT_ALL>(r2 + i, rv);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     for (int64_t t = nv * EPT; t < n; ++t) {
@@ -348,8 +417,10 @@ __global__ __launch_bounds__(256) void cg_xr_norm2_kernel(
 }  // namespace
 
 void cg_xr_norm2_hip(at::Tensor x, at::Tensor p, at::Tensor r, at::Tensor q,
-                     at::Tensor a, at::Tensor b, at::Tensor dot_out) {
+                     at::Tensor a, at::Tensor b, at::Tensor dot_out,
+                     int64_t nt) {
   int64_t n = x.numel();
+  const int mode = stream_nt_mode(nt, n * x.element_size(), "cg_xr_norm2");
   if (n == 0) return;
   const int64_t ept = std::max<int64_t>(1, 16 / x.element_size());
   int64_t blocks = (n / ept + 255) / 256 + 1;
@@ -358,10 +429,15 @@ void cg_xr_norm2_hip(at::Tensor x, at::Tensor p, at::Tensor r, at::Tensor q,
               blocks, ")");
   AT_DISPATCH_FLOATING_TYPES(x.scalar_type(), "cg_xr_norm2", [&] {
     using T = scalar_t;
-    hipLaunchKernelGGL(cg_xr_norm2_kernel<T>, dim3(blocks), dim3(256), 0,
-                       cur_stream(), x.data_ptr<T>(), p.data_ptr<T>(),
-                       r.data_ptr<T>(), q.data_ptr<T>(), a.data_ptr<T>(),
-                       b.data_ptr<T>(), dot_out.data_ptr<T>(), n);
+    auto launch = [&](auto kern) {
+      hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, cur_stream(),
+                         x.data_ptr<T>(), p.data_ptr<T>(), r.data_ptr<T>(),
+                         q.data_ptr<T>(), a.data_ptr<T>(), b.data_ptr<T>(),
+                         dot_out.data_ptr<T>(), n);
+    };
+    if (mode == NT_ALL) launch(cg_xr_norm2_kernel<T, NT_ALL>);
+    else if (mode == NT_READS) launch(cg_xr_norm2_kernel<T, NT_READS>);
+    else launch(cg_xr_norm2_kernel<T, NT_NONE>);
   });
 }
 

@@ -29,7 +29,7 @@ void ell_jacobi_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, int64_t, int64_t, int64_t, double);
 void cg_xr_norm2_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
-                     at::Tensor, at::Tensor, at::Tensor);
+                     at::Tensor, at::Tensor, at::Tensor, int64_t);
 // DIA ops: (planes, mask) is the value source — the streamed planes and no
 // mask, or the W plane constants and the row mask words
 using OptTensor = c10::optional<at::Tensor>;
@@ -63,7 +63,8 @@ void mult_compute_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                       at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                       at::Tensor);
 void mult_dense_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor);
-void axpby_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, bool, bool);
+void axpby_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, bool, bool,
+               int64_t);
 void spmm_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
               int64_t);
 void rspmm_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor);
@@ -215,7 +216,7 @@ TORCH_LIBRARY(sparse_hip, m) {
   m.def("mult_dense(Tensor indptr, Tensor indices, Tensor vals, Tensor D, "
         "Tensor(a!) out) -> ()");
   m.def("axpby(Tensor(a!) y, Tensor x, Tensor a, Tensor b, bool isalpha, "
-        "bool negate) -> ()");
+        "bool negate, int nt=-1) -> ()");
   m.def("spmv_dot(Tensor indptr, Tensor indices, Tensor values, Tensor x, "
         "Tensor(a!) y, Tensor pvec, Tensor(b!) dot_out, int col_lo) -> ()");
   m.def("axpby_norm2(Tensor(a!) y, Tensor x, Tensor a, Tensor b, bool isalpha, "
@@ -234,7 +235,7 @@ TORCH_LIBRARY(sparse_hip, m) {
         "Tensor hhi, Tensor xloc, Tensor b, Tensor dinv, Tensor(a!) xout, "
         "int W, int m, int col_lo, float omega) -> ()");
   m.def("cg_xr_norm2(Tensor(a!) x, Tensor p, Tensor(b!) r, Tensor q, "
-        "Tensor a, Tensor b, Tensor(c!) dot_out) -> ()");
+        "Tensor a, Tensor b, Tensor(c!) dot_out, int nt=-1) -> ()");
   m.def("dia_classify(Tensor dvals, Tensor(a!) cvals, Tensor(b!) mask, "
         "Tensor(c!) ok, int W) -> ()");
   m.def("dia_spmv_bpdot(Tensor planes, Tensor? mask, Tensor offs, "
