@@ -12,6 +12,8 @@ hierarchy is built once); all operator algebra (A@P, R@(AP), smoothing,
 V-cycles, CG) runs distributed on the GPUs.
 
 python examples/amg.py -n 262144 -maxiter 200
+python examples/amg.py -n 262144 -smoother gs   (multicolour Gauss-Seidel
+                                                 smoothing, one GPU)
 """
 import argparse
 import os
@@ -31,6 +33,9 @@ parser.add_argument("-theta", type=float, default=0.0)
 parser.add_argument("-maxiter", type=int, default=400)
 parser.add_argument("-tol", type=float, default=1e-8)
 parser.add_argument("-max_coarse", type=int, default=512)
+parser.add_argument("-smoother", choices=["jacobi", "gs"], default="jacobi",
+                    help="weighted Jacobi, or multicolour Gauss-Seidel "
+                         "(one GPU only)")
 # parse argv only when run as a script: importing this module (e.g. the
 # pyamg bridge reusing vcycle) must not react to the host program's argv
 args, _ = parser.parse_known_args(None if __name__ == "__main__" else [])
@@ -166,8 +171,11 @@ def comm_any(mask) -> bool:
     return bool(t.item())
 
 
-def build_hierarchy(A: csr_array, theta: float, max_coarse: int):
-    """Returns list of levels: dicts with A, P, R, dinv, omega."""
+def build_hierarchy(A: csr_array, theta: float, max_coarse: int,
+                    smoother: str = "jacobi"):
+    """Returns list of levels: dicts with A, P, R, dinv, omega and, with
+    smoother="gs", gs: the level's MulticolorGaussSeidel (colouring and
+    analysis are part of the setup)."""
     levels = []
     cur = A
     while cur.shape[0] > max_coarse and len(levels) < 20:
@@ -236,6 +244,10 @@ def build_hierarchy(A: csr_array, theta: float, max_coarse: int):
             "dinv": darray.DistArray.from_local(1.0 / d.local, d.partition, d.shape),
             "omega": omega,
         })
+        if smoother == "gs":
+            # the Galerkin operators are unstructured: coloured, not
+            # red-black by grid parity
+            levels[-1]["gs"] = linalg.MulticolorGaussSeidel(cur)
         cur = Ac
     import torch
 
@@ -287,6 +299,21 @@ def vcycle(levels, li, b, repl=None, ri=None):
     if "coarse_inv" in lvl:
         bg = b.gather() if _comm.world_size() > 1 else b.local
         return darray.asdistarray(lvl["coarse_inv"] @ bg)
+    if "gs" in lvl:
+        # two forward sweeps from x = 0 before, two backward sweeps after the
+        # coarse correction: the post-smoother is the adjoint of the
+        # pre-smoother, so the cycle stays symmetric for CG
+        import torch
+
+        A, gs = lvl["A"], lvl["gs"]
+        x = darray.DistArray.from_local(torch.zeros_like(b.local),
+                                        b.partition, b.gshape)
+        gs.sweep(x, b, "forward", 2)
+        r = A.residual(x, b)
+        rc = lvl["R"].dot(r)
+        xc = vcycle(levels, li + 1, rc, repl, ri)
+        x += lvl["P"].dot(xc)
+        return gs.sweep(x, b, "backward", 2)
     A, dinv, omega = lvl["A"], lvl["dinv"], lvl["omega"]
     x = b * dinv
     x.local.mul_(omega)
@@ -353,12 +380,16 @@ class _GraphedVcycle:
 def main():
     import math
 
+    if args.smoother == "gs" and comm.world_size() > 1:
+        sys.exit("amg: -smoother gs is not implemented at world size > 1 "
+                 "(multicolour Gauss-Seidel runs on one GPU); use "
+                 "-smoother jacobi")
     nx = int(round(args.n ** 0.5))
     A = gallery.poisson2d(nx)
     n = A.shape[0]
     b = darray.random((n,), seed=42)
     timer.start()
-    levels = build_hierarchy(A, args.theta, args.max_coarse)
+    levels = build_hierarchy(A, args.theta, args.max_coarse, args.smoother)
     setup_ms = timer.stop()
     op_complexity = sum(l["A"].nnz for l in levels) / levels[0]["A"].nnz
 

@@ -422,6 +422,29 @@ def ilu0_factor(fac, values, flag):
                       ls._order, ls._level_ptr, fac._sched, flag)
 
 
+# -- multicolour Gauss-Seidel ---------------------------------------------------
+def color_round(indptr, indices, work_in, nwork: int, seed: int, colors,
+                work_out, count):
+    """One Jones-Plassmann round over work_in[:nwork] (one launch): colours
+    what is ready in place in `colors`, appends the rest to work_out and
+    counts it in count[0] (zeroed by the caller)."""
+    ext().color_round(indptr, indices, work_in, int(nwork), int(seed), colors,
+                      work_out, count)
+
+
+def color_greedy(indptr, indices, seed: int):
+    """Sequential greedy colouring in priority order of a structurally
+    symmetric pattern (host tensors, CPU-dispatched); int32 colours."""
+    return ext().color_greedy(indptr, indices, int(seed))
+
+
+def mcgs_sweep(gs, values, diag, b, x, backward: bool):
+    """One pass over all colours of a gauss_seidel.MulticolorGaussSeidel in
+    place in x: one launch per colour on the current stream, no host sync."""
+    ext().mcgs_sweep(gs._indptr, gs._indices, values, diag, gs._order,
+                     gs._sched, b, x, bool(backward))
+
+
 # -- device-DIA fast path -----------------------------------------------------
 _DIA_CONST_DTYPES = (torch.float32, torch.float64)
 

@@ -3,6 +3,8 @@
 // Loaded via torch.ops.load_library from sparse/kernels/_build/sparse_hip.so;
 // Python wrappers live in sparse/kernels/__init__.py.
 #include <algorithm>
+#include <cstdint>
+#include <vector>
 
 #include <torch/library.h>
 
@@ -93,6 +95,10 @@ void trsv_solve_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, at::Tensor);
 void ilu0_factor_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                      at::Tensor, at::Tensor, at::Tensor, at::Tensor);
+void color_round_hip(at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
+                     at::Tensor, at::Tensor, at::Tensor);
+void mcgs_sweep_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                    at::Tensor, at::Tensor, at::Tensor, bool);
 
 // Dependency levels of a strict-triangle CSR, one sequential O(nnz) pass on
 // the host (setup path of sparse/trisolve.py): levels[i] = 0 for a row with
@@ -137,6 +143,73 @@ at::Tensor trsv_levels_cpu(at::Tensor indptr, at::Tensor indices, bool lower) {
                      levels.data_ptr<int64_t>());
   }
   return levels;
+}
+
+// Sequential greedy colouring in priority order on the host (the host twin
+// of color.hip; backs sparse/gauss_seidel.py without a GPU).  The pattern is
+// structurally symmetric (the caller symmetrises), diagonal entries are
+// skipped.  Vertices are visited by decreasing (h(i), i), h the 32-bit hash
+// of color.hip, and each takes the smallest colour no coloured neighbour has.
+static inline uint32_t color_hash_host(uint32_t i, uint32_t seed) {
+  uint32_t x = i ^ seed;
+  x ^= x >> 16;
+  x *= 0x7feb352du;
+  x ^= x >> 15;
+  x *= 0x846ca68bu;
+  x ^= x >> 16;
+  return x;
+}
+
+template <typename I>
+static void color_greedy_impl(const int64_t* ip, const I* ix, int64_t n,
+                              uint32_t seed, int32_t* color) {
+  std::vector<int64_t> visit(n);
+  std::vector<uint32_t> h(n);
+  for (int64_t i = 0; i < n; ++i) {
+    visit[i] = i;
+    h[i] = color_hash_host(static_cast<uint32_t>(i), seed);
+  }
+  std::sort(visit.begin(), visit.end(), [&](int64_t a, int64_t b) {
+    return h[a] != h[b] ? h[a] > h[b] : a > b;
+  });
+  // stamp[c] == s + 1: colour c is taken around the s-th visited vertex; a
+  // vertex of degree d finds a free colour among 0..d
+  std::vector<int64_t> stamp(n + 1, 0);
+  for (int64_t s = 0; s < n; ++s) {
+    const int64_t i = visit[s];
+    for (int64_t p = ip[i]; p < ip[i + 1]; ++p) {
+      const int64_t j = static_cast<int64_t>(ix[p]);
+      TORCH_CHECK(0 <= j && j < n, "color_greedy: column outside the matrix");
+      if (j != i && color[j] >= 0) stamp[color[j]] = s + 1;
+    }
+    int32_t c = 0;
+    while (stamp[c] == s + 1) ++c;
+    color[i] = c;
+  }
+}
+
+at::Tensor color_greedy_cpu(at::Tensor indptr, at::Tensor indices,
+                            int64_t seed) {
+  TORCH_CHECK(indptr.scalar_type() == at::kLong && indptr.numel() >= 1 &&
+                  indptr.is_contiguous() && indices.is_contiguous(),
+              "color_greedy: bad structure tensors");
+  const int64_t n = indptr.numel() - 1;
+  const int64_t* ip = indptr.data_ptr<int64_t>();
+  TORCH_CHECK(ip[0] == 0 && ip[n] == indices.numel(),
+              "color_greedy: indptr does not match indices");
+  for (int64_t i = 0; i < n; ++i)
+    TORCH_CHECK(ip[i] <= ip[i + 1], "color_greedy: indptr not monotone");
+  at::Tensor colors = at::full({n}, -1, indptr.options().dtype(at::kInt));
+  if (indices.scalar_type() == at::kInt) {
+    color_greedy_impl(ip, indices.data_ptr<int32_t>(), n,
+                      static_cast<uint32_t>(seed), colors.data_ptr<int32_t>());
+  } else {
+    TORCH_CHECK(indices.scalar_type() == at::kLong,
+                "color_greedy: indices must be int32 or int64");
+    color_greedy_impl(ip, indices.data_ptr<int64_t>(), n,
+                      static_cast<uint32_t>(seed), colors.data_ptr<int32_t>());
+  }
+  return colors;
 }
 
 // Sequential IKJ ILU(0) on the host, in place in v (the host twin of
@@ -298,6 +371,13 @@ TORCH_LIBRARY(sparse_hip, m) {
   m.def("ilu0_factor(Tensor indptr, Tensor indices, Tensor(a!) values, "
         "Tensor diag_ptr, Tensor order, Tensor level_ptr, Tensor sched, "
         "Tensor(b!) flag) -> ()");
+  m.def("color_round(Tensor indptr, Tensor indices, Tensor work_in, "
+        "int nwork, int seed, Tensor(a!) colors, Tensor(b!) work_out, "
+        "Tensor(c!) count) -> ()");
+  m.def("color_greedy(Tensor indptr, Tensor indices, int seed) -> Tensor");
+  m.def("mcgs_sweep(Tensor indptr, Tensor indices, Tensor values, "
+        "Tensor diag, Tensor order, Tensor sched, Tensor b, Tensor(a!) x, "
+        "bool backward) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
@@ -339,9 +419,12 @@ TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
   m.impl("spgemm_compute", spgemm_compute_hip);
   m.impl("trsv_solve", trsv_solve_hip);
   m.impl("ilu0_factor", ilu0_factor_hip);
+  m.impl("color_round", color_round_hip);
+  m.impl("mcgs_sweep", mcgs_sweep_hip);
 }
 
 TORCH_LIBRARY_IMPL(sparse_hip, CPU, m) {
   m.impl("trsv_levels", trsv_levels_cpu);
   m.impl("ilu0_factor", ilu0_factor_cpu);
+  m.impl("color_greedy", color_greedy_cpu);
 }

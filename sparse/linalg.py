@@ -32,7 +32,8 @@ __all__ = [
     "LinearOperator", "IdentityOperator", "aslinearoperator", "cg", "cgs",
     "bicg", "bicgstab", "gmres", "minres", "lsqr", "eigsh", "svds",
     "spsolve", "cg_axpby", "norm", "spsolve_triangular", "TriangularSolver",
-    "sgs_preconditioner", "ilu0", "ILU0",
+    "sgs_preconditioner", "ilu0", "ILU0", "MulticolorGaussSeidel",
+    "greedy_coloring",
 ]
 
 
@@ -1000,3 +1001,7 @@ from .trisolve import (  # noqa: E402,F401
 
 # -- ILU(0) preconditioner (sparse/ilu.py) -------------------------------------
 from .ilu import ILU0, ilu0  # noqa: E402,F401
+
+# -- multicolour Gauss-Seidel (sparse/gauss_seidel.py) -------------------------
+from .gauss_seidel import (  # noqa: E402,F401
+    MulticolorGaussSeidel, greedy_coloring)

@@ -301,8 +301,21 @@ class _SGSOperator(LinearOperator):
     rmatvec = matvec
 
 
-def sgs_preconditioner(A) -> LinearOperator:
-    """Symmetric Gauss-Seidel preconditioner of A as a LinearOperator:
-    two triangular solves over A itself and one diagonal scale."""
+def sgs_preconditioner(A, ordering: str = "natural",
+                       seed: int = 0) -> LinearOperator:
+    """Symmetric Gauss-Seidel preconditioner of A as a LinearOperator.
+
+    ordering="natural": two triangular solves over A itself and one diagonal
+    scale, in the row order of A.  ordering="multicolor": the same
+    preconditioner in the order of a greedy colouring of A (seed as in
+    greedy_coloring), one launch per colour and direction — a
+    gauss_seidel.MulticolorGaussSeidel."""
     _single_rank("sgs_preconditioner")
-    return _SGSOperator(A)
+    if ordering == "natural":
+        return _SGSOperator(A)
+    if ordering == "multicolor":
+        from .gauss_seidel import MulticolorGaussSeidel
+
+        return MulticolorGaussSeidel(A, seed=seed)
+    raise ValueError(
+        f"ordering must be 'natural' or 'multicolor', got {ordering!r}")
