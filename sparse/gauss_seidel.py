@@ -28,8 +28,9 @@ colouring (colors=) is validated on the device: this is what makes the
 in-place sweeps race-free.  The matrix arrays are referenced, not copied; the
 diagonal is extracted once, so a matrix whose values change needs a new
 object (the colouring can be passed back in).  sweep() enqueues one launch
-per colour on the current stream (kernels/src/mcgs.hip) and never
-synchronises with the host.
+per colour on the current stream (kernels/src/relax.hip) and never
+synchronises with the host.  The steps shared with the triangular solve and
+ILU(0) are in sparse/rowsched.py.
 """
 from __future__ import annotations
 
@@ -38,9 +39,10 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from . import rowsched
 from .darray import DistArray, asdistarray
 from .linalg import LinearOperator
-from .trisolve import _as_csr, _row_group, _single_rank
+from .trisolve import _row_group
 from .types import common_value_dtype, to_numpy_dtype
 
 __all__ = ["MulticolorGaussSeidel", "greedy_coloring"]
@@ -87,9 +89,7 @@ def _graph(A) -> Tuple[torch.Tensor, torch.Tensor]:
     dev = lc.values.device
     indptr = lc.indptr.to(torch.int64).contiguous()
     indices = lc.indices.contiguous()
-    counts = indptr[1:] - indptr[:-1]
-    rows = torch.repeat_interleave(
-        torch.arange(n, dtype=torch.int64, device=dev), counts)
+    _, rows = rowsched.row_index(indptr)
     cols = indices.long()
     outside = ((cols < 0) | (cols >= n)).any()
     off = rows != cols
@@ -157,10 +157,7 @@ def greedy_coloring(A, seed: int = 0) -> torch.Tensor:
     """Colours 0..C-1 of the rows of the square matrix A as an int32 tensor
     on A's device: the greedy colouring in decreasing (h(i), i) priority of
     the graph of A ∪ Aᵀ (module docstring)."""
-    _single_rank("greedy_coloring")
-    A = _as_csr(A)
-    if A.shape[0] != A.shape[1]:
-        raise ValueError(f"A must be square, got shape {A.shape}")
+    A = rowsched.square_csr(A, "greedy_coloring")
     return _greedy_coloring(A, int(seed))[0]
 
 
@@ -173,10 +170,7 @@ class MulticolorGaussSeidel(LinearOperator):
     the multicolour symmetric Gauss-Seidel preconditioner."""
 
     def __init__(self, A, colors=None, seed: int = 0):
-        _single_rank("MulticolorGaussSeidel")
-        A = _as_csr(A)
-        if A.shape[0] != A.shape[1]:
-            raise ValueError(f"A must be square, got shape {A.shape}")
+        A = rowsched.square_csr(A, "MulticolorGaussSeidel")
         n = A.shape[0]
         super().__init__(A.shape, dtype=A.dtype)
         lc = A.local
@@ -193,23 +187,15 @@ class MulticolorGaussSeidel(LinearOperator):
         self._values = lc.values.contiguous()
 
         # 1. diagonal: the sum of the stored diagonal entries of each row
-        counts = self._indptr[1:] - self._indptr[:-1]
-        rows = torch.repeat_interleave(
-            torch.arange(n, dtype=torch.int64, device=dev), counts)
+        counts, rows = rowsched.row_index(self._indptr)
         cols = self._indices.long()
         on = cols == rows
-        diag = torch.zeros(n, dtype=self._values.dtype, device=dev)
-        diag.index_add_(0, rows[on], self._values[on])
-        # one device reduction, one host read (the sweeps index x with the
-        # columns unchecked)
-        outside, singular = torch.stack(
-            [((cols < 0) | (cols >= n)).any(), (diag == 0).any()]).tolist()
-        if outside:
-            raise ValueError("A has column indices outside the matrix")
-        if singular:
-            raise np.linalg.LinAlgError(
-                "A is singular: zero or missing entry on the diagonal")
-        self._diag = diag
+        # one device reduction, one host read: the columns ride with the
+        # diagonal's check (the sweeps index x with the columns unchecked)
+        outside = ((cols < 0) | (cols >= n)).any()
+        self._diag = rowsched.summed_diagonal(
+            on, rows, self._values, n, first=[(outside, ValueError(
+                "A has column indices outside the matrix"))])
         self._cast = {}  # value dtype -> (values, diag) for a wider x
         self._host = {}  # numpy dtype -> per-colour scipy operands
 
@@ -242,24 +228,13 @@ class MulticolorGaussSeidel(LinearOperator):
         self._colors = col.contiguous()
 
         # 3. rows by (colour, row), class boundaries, lanes per row
-        order = torch.sort(self._colors, stable=True).indices
-        if n < 2**31:
-            order = order.to(torch.int32)
-        self._order = order.contiguous()
-        widths = torch.bincount(self._colors.long())  # host read of C
-        self._ncolors = int(widths.numel())
-        self._color_ptr = torch.zeros(self._ncolors + 1, dtype=torch.int64,
-                                      device=dev)
-        torch.cumsum(widths, 0, out=self._color_ptr[1:])
-        cs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts[self._order.long()], 0, out=cs[1:])
-        cp = self._color_ptr.cpu().numpy()
-        nnz = np.diff(cs[self._color_ptr].cpu().numpy())
-        sched = np.zeros((self._ncolors, 3), dtype=np.int64)
-        for c in range(self._ncolors):
-            w = cp[c + 1] - cp[c]
-            sched[c] = (cp[c], cp[c + 1], _row_group(nnz[c] / max(w, 1)))
-        self._sched = torch.from_numpy(sched)
+        cl = self._classes = rowsched.RowClasses(self._colors, dev)
+        self._order = cl.order
+        self._ncolors = cl.nclasses
+        self._color_ptr = cl.ptr
+        self._sched = rowsched.schedule_rows(
+            cl.ptr_host, cl.sums(counts),
+            rowsched.plain_segments(cl.nclasses), _row_group)
 
     # -- read-only analysis results -------------------------------------------
     @property
@@ -282,13 +257,6 @@ class MulticolorGaussSeidel(LinearOperator):
         return self._color_ptr
 
     # -- sweeps ---------------------------------------------------------------
-    def _operands(self, tdt):
-        if tdt == self._values.dtype:
-            return self._values, self._diag
-        if tdt not in self._cast:
-            self._cast[tdt] = (self._values.to(tdt), self._diag.to(tdt))
-        return self._cast[tdt]
-
     def sweep(self, x, b, direction: str = "forward",
               iterations: int = 1) -> DistArray:
         """Gauss-Seidel sweeps in place in x, which is returned: for every
@@ -325,7 +293,8 @@ class MulticolorGaussSeidel(LinearOperator):
         if self._gpu:
             from . import kernels
 
-            vals, diag = self._operands(x.dtype)
+            vals, diag = rowsched.cast_operands(self._cast, self._values,
+                                                self._diag, x.dtype)
             for _ in range(iterations):
                 for backward in passes:
                     kernels.mcgs_sweep(self, vals, diag, b, x, backward)
@@ -357,7 +326,7 @@ class MulticolorGaussSeidel(LinearOperator):
             # coo -> csr sums duplicates
             S = sps.csr_matrix((v[off], (r[off], c[off])), shape=(n, n))
             order = self._order.numpy().astype(np.int64)
-            cp = self._color_ptr.numpy()
+            cp = self._classes.ptr_host
             per_color = []
             for k in range(self._ncolors):
                 rows = order[cp[k]: cp[k + 1]]
@@ -370,29 +339,14 @@ class MulticolorGaussSeidel(LinearOperator):
     def matvec(self, r, out: Optional[DistArray] = None) -> DistArray:
         """One symmetric sweep from x = 0: the multicolour SGS preconditioner
         applied to r of shape (n,) or (n, k)."""
-        r = asdistarray(r)
-        n = self.shape[0]
-        if r.ndim not in (1, 2) or r.shape[0] != n:
-            raise ValueError(
-                f"r has shape {r.shape}, expected ({n},) or ({n}, k)")
+        r = rowsched.as_rhs(r, self.shape[0], "r")
         tdt = common_value_dtype(self._values.dtype, r.local.dtype)
-        direct = (out is not None and out.local.dtype == tdt
-                  and out.shape == r.shape and out.local.is_contiguous())
+        x, direct = rowsched.result_buffer(r, out, tdt)
         b = r.local.to(tdt).contiguous()
-        if direct:
-            x = out.local
-            if b.data_ptr() == x.data_ptr():  # out aliases r
-                b = b.clone()
-            x.zero_()
-        else:
-            x = torch.zeros(b.shape, dtype=tdt, device=b.device)
+        if b.data_ptr() == x.data_ptr():  # out aliases r
+            b = b.clone()
+        x.zero_()
         self._sweep_local(x, b, "symmetric", 1)
-        if direct:
-            return out
-        res = DistArray.from_local(x, r.partition, r.shape)
-        if out is not None:
-            out.local.copy_(res.local.to(out.local.dtype))
-            return out
-        return res
+        return rowsched.finish_result(x, direct, r, out)
 
     rmatvec = matvec

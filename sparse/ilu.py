@@ -28,9 +28,10 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
+from . import rowsched
 from .darray import DistArray
 from .linalg import LinearOperator
-from .trisolve import TriangularSolver, _as_csr, _single_rank
+from .trisolve import TriangularSolver
 
 __all__ = ["ILU0", "ilu0"]
 
@@ -75,14 +76,10 @@ class ILU0(LinearOperator):
     solve(r, out=None) == U⁻¹ L⁻¹ r.  Not cached on the matrix."""
 
     def __init__(self, A):
-        _single_rank("ilu0")
-        A = _as_csr(A)
-        if A.shape[0] != A.shape[1]:
-            raise ValueError(f"A must be square, got shape {A.shape}")
+        A = rowsched.square_csr(A, "ilu0")
         super().__init__(A.shape, dtype=A.dtype)
         n = A.shape[0]
         lc = A.local
-        dev = lc.values.device
         from . import kernels
 
         self._gpu = lc.values.is_cuda
@@ -93,9 +90,7 @@ class ILU0(LinearOperator):
         self._indices = lc.indices.contiguous()
 
         # 1. structure: sorted duplicate-free rows with a stored diagonal
-        counts = self._indptr[1:] - self._indptr[:-1]
-        rows = torch.repeat_interleave(
-            torch.arange(n, dtype=torch.int64, device=dev), counts)
+        counts, rows = rowsched.row_index(self._indptr)
         cols = self._indices.long()
         unsorted = ((cols < 0) | (cols >= n)).any()
         if cols.numel() > 1:
@@ -123,16 +118,10 @@ class ILU0(LinearOperator):
         ls = self._Ls
 
         # 3. the same segments with lanes per row from the full row length
-        chain, starts, ends = ls._seg
-        cs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(counts[ls._order.long()], 0, out=cs[1:])
-        lp = ls._level_ptr.cpu().numpy()
-        cs_h = cs[ls._level_ptr].cpu().numpy()
-        sched = np.zeros((len(starts), 4), dtype=np.int64)
-        for s, (c, lo, hi) in enumerate(zip(chain, starts, ends)):
-            g = _ilu0_group((cs_h[hi] - cs_h[lo]) / max(lp[hi] - lp[lo], 1))
-            sched[s] = (1, lo, hi, g) if c else (0, lp[lo], lp[hi], g)
-        self._sched = torch.from_numpy(sched)
+        cl = ls._classes
+        self._sched = rowsched.schedule_rows(
+            cl.ptr_host, cl.sums(counts), ls._seg, _ilu0_group,
+            chain_group=_ilu0_group)
 
         # 4. numeric phase
         self._fvals = torch.empty_like(lc.values)
@@ -173,7 +162,7 @@ class ILU0(LinearOperator):
         """New values on the SAME structure: numeric phase only.  After a
         LinAlgError (zero pivot) the factors are unusable until the next
         successful refactor."""
-        A = _as_csr(A)
+        A = rowsched.as_csr(A)
         if tuple(A.shape) != self.shape:
             raise ValueError(
                 f"refactor: shape {A.shape} differs from {self.shape}")

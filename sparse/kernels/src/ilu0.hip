@@ -11,7 +11,7 @@
 // Row k is in the strict lower pattern of row i, so it belongs to an earlier
 // level of the lower-triangle level schedule (the one the L solver uses:
 // `order`, `level_ptr`, same chain cut), and rows of one level never read
-// each other.  As in trsv.hip the levels run as
+// each other.  As in relax.hip the levels run as
 //  - ilu0_level_kernel   one launch per WIDE level; the rows it reads were
 //                        finished by earlier launches on the stream.
 //  - ilu0_chain_kernel   one launch, ONE 1024-thread workgroup, for a run of
@@ -49,18 +49,9 @@
 //
 // `vals` is deliberately NOT __restrict__ / const: rows read earlier rows of
 // the array they write.
-#include "common.h"
+#include "rowsched.h"
 
 namespace {
-
-constexpr int ILU0_BLOCK = 256;
-constexpr int ILU0_CHAIN_THREADS = 1024;
-
-__device__ __forceinline__ int64_t ilu0_order_at(const void* order, bool o64,
-                                                 int64_t i) {
-  return o64 ? static_cast<const int64_t*>(order)[i]
-             : static_cast<int64_t>(static_cast<const int32_t*>(order)[i]);
-}
 
 // value of lane `src` of the G-lane row group, in every lane of the group
 template <int G, typename T>
@@ -140,25 +131,25 @@ __device__ __forceinline__ void ilu0_row(
 
 // One wide level: rows order[row_lo + ri], ri < nrows, G lanes per row.
 template <typename T, typename I, int G>
-__global__ __launch_bounds__(ILU0_BLOCK) void ilu0_level_kernel(
+__global__ __launch_bounds__(ROWSCHED_BLOCK) void ilu0_level_kernel(
     const int64_t* __restrict__ indptr, const I* __restrict__ indices,
     T* vals, const int64_t* __restrict__ diag_ptr,
     const void* __restrict__ order, bool o64, int64_t n, int64_t row_lo,
     int64_t nrows, long long* flag) {
-  const int64_t tid = (int64_t)blockIdx.x * ILU0_BLOCK + threadIdx.x;
+  const int64_t tid = (int64_t)blockIdx.x * ROWSCHED_BLOCK + threadIdx.x;
   const int64_t ri = tid / G;
   const int g = (int)(tid % G);
   if (ri >= nrows) return;  // the G lanes of a group leave together
   ilu0_row<T, I, G>(indptr, indices, vals, diag_ptr, n,
-                    ilu0_order_at(order, o64, row_lo + ri), g, flag);
+                    order_at(order, o64, row_lo + ri), g, flag);
 }
 
-// Levels [level_lo, level_hi), each at most ILU0_CHAIN_THREADS rows, in ONE
-// workgroup: the group of G threads starting at thread t takes row t / G of
+// Levels [level_lo, level_hi), each at most ROWSCHED_CHAIN_THREADS rows, in
+// ONE workgroup: the group of G threads starting at thread t takes row t / G of
 // the level and strides by the block size; a workgroup barrier separates
 // levels.  Launched with a grid of exactly one block.
 template <typename T, typename I, int G>
-__global__ __launch_bounds__(ILU0_CHAIN_THREADS) void ilu0_chain_kernel(
+__global__ __launch_bounds__(ROWSCHED_CHAIN_THREADS) void ilu0_chain_kernel(
     const int64_t* __restrict__ indptr, const I* __restrict__ indices,
     T* vals, const int64_t* __restrict__ diag_ptr,
     const void* __restrict__ order, bool o64, int64_t n,
@@ -168,11 +159,11 @@ __global__ __launch_bounds__(ILU0_CHAIN_THREADS) void ilu0_chain_kernel(
   for (int64_t l = level_lo; l < level_hi; ++l) {
     const int64_t base = level_ptr[l];
     const int64_t width = level_ptr[l + 1] - base;
-    // ILU0_CHAIN_THREADS is a multiple of G: a group is whole in or out
+    // ROWSCHED_CHAIN_THREADS is a multiple of G: a group is whole in or out
     for (int64_t ri = threadIdx.x / G; ri < width;
-         ri += ILU0_CHAIN_THREADS / G)
+         ri += ROWSCHED_CHAIN_THREADS / G)
       ilu0_row<T, I, G>(indptr, indices, vals, diag_ptr, n,
-                        ilu0_order_at(order, o64, base + ri), g, flag);
+                        order_at(order, o64, base + ri), g, flag);
     // all threads of the block reach this barrier every level (the loop
     // bounds are uniform); it orders this level's value stores before the
     // next level's loads of them within the workgroup
@@ -182,9 +173,8 @@ __global__ __launch_bounds__(ILU0_CHAIN_THREADS) void ilu0_chain_kernel(
 
 }  // namespace
 
-// sched: host (CPU) int64 tensor (nseg, 4), one row per segment:
-//   wide  {0, row_lo, row_hi, G}      rows order[row_lo:row_hi], one level
-//   chain {1, level_lo, level_hi, G}  levels [level_lo, level_hi)
+// sched: the level schedule of rowsched.h, G used by wide and chain segments
+// alike.
 // flag: one int64 word on the device, pre-set by the caller to a value >= n;
 // the smallest row index with a zero pivot is atomicMin'ed into it.
 // All launches go to the current stream in schedule order; nothing here
@@ -192,53 +182,21 @@ __global__ __launch_bounds__(ILU0_CHAIN_THREADS) void ilu0_chain_kernel(
 void ilu0_factor_hip(at::Tensor indptr, at::Tensor indices, at::Tensor values,
                      at::Tensor diag_ptr, at::Tensor order,
                      at::Tensor level_ptr, at::Tensor sched, at::Tensor flag) {
+  constexpr const char* OP = "ilu0_factor";
   const int64_t n = indptr.numel() - 1;
-  TORCH_CHECK(!sched.is_cuda() && sched.scalar_type() == at::kLong &&
-                  sched.dim() == 2 && sched.size(1) == 4 &&
-                  sched.is_contiguous(),
-              "ilu0_factor: sched must be a contiguous CPU int64 (nseg, 4)");
-  TORCH_CHECK(values.is_cuda() && values.is_contiguous(),
-              "ilu0_factor: values must be a contiguous device tensor");
-  for (const at::Tensor& t :
-       {indptr, indices, diag_ptr, order, level_ptr, flag})
-    TORCH_CHECK(t.is_cuda() && t.device() == values.device() &&
-                    t.is_contiguous(),
-                "ilu0_factor: operands must be contiguous and on the values' "
-                "device");
-  TORCH_CHECK(n >= 0 && diag_ptr.numel() == n && order.numel() == n &&
-                  indices.numel() == values.numel() &&
-                  indptr.scalar_type() == at::kLong &&
-                  diag_ptr.scalar_type() == at::kLong &&
-                  level_ptr.scalar_type() == at::kLong &&
-                  level_ptr.numel() >= 1 &&
+  const bool o64 = rowsched_check_operands(
+      OP, values, {indptr, indices, diag_ptr, order, flag}, indptr, indices,
+      values, order, level_ptr);
+  TORCH_CHECK(diag_ptr.numel() == n && diag_ptr.scalar_type() == at::kLong &&
                   flag.scalar_type() == at::kLong && flag.numel() == 1,
-              "ilu0_factor: bad analysis tensors");
-  if (n == 0 || sched.size(0) == 0) return;
-  const int64_t nlevels = level_ptr.numel() - 1;
-  const bool o64 = order.scalar_type() == at::kLong;
-  TORCH_CHECK(o64 || order.scalar_type() == at::kInt,
-              "ilu0_factor: order must be int32 or int64");
-  const int64_t* sc = sched.data_ptr<int64_t>();
-  const int64_t nseg = sched.size(0);
-  // validate the whole schedule against the analysis sizes before the first
-  // launch: the kernels index order/level_ptr with these bounds unchecked
+              OP, ": bad analysis tensors");
   // (row indices, diag_ptr and lower columns are checked in the kernel)
-  for (int64_t s = 0; s < nseg; ++s) {
-    const int64_t kind = sc[4 * s], lo = sc[4 * s + 1], hi = sc[4 * s + 2],
-                  G = sc[4 * s + 3];
-    TORCH_CHECK(G == 1 || G == 8 || G == 64, "ilu0_factor: bad row group");
-    if (kind == 0) {
-      TORCH_CHECK(0 <= lo && lo <= hi && hi <= n,
-                  "ilu0_factor: bad wide segment");
-    } else {
-      TORCH_CHECK(kind == 1 && 0 <= lo && lo <= hi && hi <= nlevels,
-                  "ilu0_factor: bad chain segment");
-    }
-  }
+  rowsched_check_schedule(OP, sched, n, level_ptr, true);
+  if (n == 0 || sched.size(0) == 0) return;
   hipStream_t stream = cur_stream();
-  DISPATCH_VALUES(values.scalar_type(), "ilu0_factor", [&] {
+  DISPATCH_VALUES(values.scalar_type(), OP, [&] {
     using T = scalar_t;
-    DISPATCH_INDEX(indices.scalar_type(), "ilu0_factor", [&] {
+    DISPATCH_INDEX(indices.scalar_type(), OP, [&] {
       const int64_t* ip = indptr.data_ptr<int64_t>();
       const index_t* ix = indices.data_ptr<index_t>();
       T* av = values.data_ptr<T>();
@@ -246,28 +204,24 @@ void ilu0_factor_hip(at::Tensor indptr, at::Tensor indices, at::Tensor values,
       const void* ord = order.data_ptr();
       const int64_t* lp = level_ptr.data_ptr<int64_t>();
       long long* fl = reinterpret_cast<long long*>(flag.data_ptr<int64_t>());
-      for (int64_t s = 0; s < nseg; ++s) {
-        const int64_t kind = sc[4 * s], lo = sc[4 * s + 1], hi = sc[4 * s + 2],
-                      G = sc[4 * s + 3];
-        if (hi <= lo) continue;  // empty segment: no launch
-        auto launch = [&](auto gg) {
+      rowsched_for_each(sched, false, [&](int64_t kind, int64_t lo,
+                                          int64_t hi, int64_t G) {
+        rowsched_with_group(G, [&](auto gg) {
           constexpr int GG = decltype(gg)::value;
           if (kind == 1) {
             hipLaunchKernelGGL((ilu0_chain_kernel<T, index_t, GG>), dim3(1),
-                               dim3(ILU0_CHAIN_THREADS), 0, stream, ip, ix, av,
-                               dg, ord, o64, n, lp, lo, hi, fl);
+                               dim3(ROWSCHED_CHAIN_THREADS), 0, stream, ip, ix,
+                               av, dg, ord, o64, n, lp, lo, hi, fl);
           } else {
             const int64_t nrows = hi - lo;
-            const int64_t blocks = (nrows * GG + ILU0_BLOCK - 1) / ILU0_BLOCK;
+            const int64_t blocks =
+                (nrows * GG + ROWSCHED_BLOCK - 1) / ROWSCHED_BLOCK;
             hipLaunchKernelGGL((ilu0_level_kernel<T, index_t, GG>),
-                               dim3(blocks), dim3(ILU0_BLOCK), 0, stream, ip,
-                               ix, av, dg, ord, o64, n, lo, nrows, fl);
+                               dim3(blocks), dim3(ROWSCHED_BLOCK), 0, stream,
+                               ip, ix, av, dg, ord, o64, n, lo, nrows, fl);
           }
-        };
-        if (G == 1) launch(std::integral_constant<int, 1>{});
-        else if (G == 8) launch(std::integral_constant<int, 8>{});
-        else launch(std::integral_constant<int, 64>{});
-      }
+        });
+      });
     });
   });
   SPARSE_CHECK_HIP(hipGetLastError());

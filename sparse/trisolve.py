@@ -14,7 +14,8 @@ maximal run of consecutive levels of at most TRSV_CHAIN_WIDTH rows each is one
 "chain" segment (one launch of a single workgroup that steps through the
 levels with a barrier), every other level is its own "wide" segment (one
 launch).  Solving enqueues the schedule on the current stream and never
-synchronises with the host (kernels/src/trsv.hip).
+synchronises with the host (kernels/src/relax.hip).  The steps shared with
+ILU(0) and the multicolour sweeps are in sparse/rowsched.py.
 
 Semantics: only the selected triangle is read (so SGS can use A itself);
 duplicate stored entries add up, on the diagonal too; unit_diagonal ignores
@@ -29,9 +30,10 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .darray import DistArray, asdistarray
+from . import rowsched
+from .darray import DistArray
 from .linalg import LinearOperator
-from .parallel import comm
+from .rowsched import as_csr, single_rank
 from .types import common_value_dtype, to_numpy_dtype
 from .utils import perf_warning
 
@@ -41,23 +43,6 @@ __all__ = ["TRSV_CHAIN_WIDTH", "TriangularSolver", "spsolve_triangular",
 # levels of at most this many rows are stepped through inside one workgroup;
 # wider ones get a launch of their own
 TRSV_CHAIN_WIDTH = 1024
-
-
-def _single_rank(what: str) -> None:
-    if comm.world_size() > 1:
-        raise NotImplementedError(
-            f"{what} is not implemented at world size > 1: rows depend on "
-            "rows of other ranks' slabs (a per-slab block-Jacobi variant is "
-            "out of scope)")
-
-
-def _as_csr(A):
-    from .csr import csr_array
-    from .module import is_sparse_matrix
-
-    if isinstance(A, csr_array):
-        return A
-    return A.tocsr() if is_sparse_matrix(A) else csr_array(A)
 
 
 def _levels_numpy(indptr: np.ndarray, indices: np.ndarray,
@@ -84,10 +69,7 @@ class TriangularSolver(LinearOperator):
     for the lower (or upper) triangle T of A."""
 
     def __init__(self, A, lower: bool = True, unit_diagonal: bool = False):
-        _single_rank("TriangularSolver")
-        A = _as_csr(A)
-        if A.shape[0] != A.shape[1]:
-            raise ValueError(f"A must be square, got shape {A.shape}")
+        A = rowsched.square_csr(A, "TriangularSolver")
         n = A.shape[0]
         super().__init__(A.shape, dtype=A.dtype)
         self.lower = bool(lower)
@@ -101,20 +83,12 @@ class TriangularSolver(LinearOperator):
             kernels.require()
 
         # 1. split the triangle: strict CSR (original row order) + diagonal
-        counts = lc.indptr[1:] - lc.indptr[:-1]
-        rows = torch.repeat_interleave(
-            torch.arange(n, dtype=torch.int64, device=dev), counts)
+        _, rows = rowsched.row_index(lc.indptr)
         cols = lc.indices.long()
         if unit_diagonal:
             diag = torch.ones(n, dtype=lc.values.dtype, device=dev)
-        else:
-            on = cols == rows
-            diag = torch.zeros(n, dtype=lc.values.dtype, device=dev)
-            diag.index_add_(0, rows[on], lc.values[on])
-            # one device reduction, one host read
-            if bool((diag == 0).any().item()):
-                raise np.linalg.LinAlgError(
-                    "A is singular: zero or missing entry on the diagonal")
+        else:  # one device reduction, one host read
+            diag = rowsched.summed_diagonal(cols == rows, rows, lc.values, n)
         strict = cols < rows if lower else cols > rows
         self._indices = lc.indices[strict].contiguous()
         self._values = lc.values[strict].contiguous()
@@ -134,37 +108,17 @@ class TriangularSolver(LinearOperator):
             levels = torch.from_numpy(
                 _levels_numpy(ip_h.numpy(), ix_h.numpy(), self.lower))
         self._levels = levels
-        lv = levels.numpy()
-        self._nlevels = int(lv.max()) + 1 if n else 0
 
         # 3. row order by (level, row), level boundaries, schedule
-        widths = np.bincount(lv, minlength=self._nlevels).astype(np.int64)
-        lp = np.zeros(self._nlevels + 1, dtype=np.int64)
-        np.cumsum(widths, out=lp[1:])
-        order = torch.sort(levels.to(dev), stable=True).indices
-        if n < 2**31:
-            order = order.to(torch.int32)
-        self._order = order
-        self._level_ptr = torch.from_numpy(lp).to(dev)
-        rowlen = (self._indptr[1:] - self._indptr[:-1])[order.long()]
-        cs = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        torch.cumsum(rowlen, 0, out=cs[1:])
-        level_nnz = np.diff(cs[self._level_ptr].cpu().numpy())
-        small = widths <= TRSV_CHAIN_WIDTH
-        # a level opens a segment unless it and its predecessor are both small
-        starts = np.flatnonzero(np.r_[True, ~(small[1:] & small[:-1])]) \
-            if self._nlevels else np.zeros(0, dtype=np.int64)
-        ends = np.r_[starts[1:], self._nlevels].astype(np.int64)
-        chain = small[starts] if self._nlevels else np.zeros(0, dtype=bool)
-        self._seg = (chain, starts, ends)
-        sched = np.zeros((len(starts), 4), dtype=np.int64)
-        for s, (c, lo, hi) in enumerate(zip(chain, starts, ends)):
-            if c:
-                sched[s] = (1, lo, hi, 0)
-            else:  # hi == lo + 1
-                sched[s] = (0, lp[lo], lp[hi],
-                            _row_group(level_nnz[lo] / widths[lo]))
-        self._sched = torch.from_numpy(sched)
+        cl = self._classes = rowsched.RowClasses(levels, dev)
+        self._nlevels = cl.nclasses
+        self._order = cl.order
+        self._level_ptr = cl.ptr
+        self._seg = rowsched.chain_segments(np.diff(cl.ptr_host),
+                                            TRSV_CHAIN_WIDTH)
+        level_nnz = cl.sums(self._indptr[1:] - self._indptr[:-1])
+        self._sched = rowsched.schedule_rows(cl.ptr_host, level_nnz,
+                                             self._seg, _row_group)
 
         # 4. inherently sequential structure
         if self._nlevels > n / 32:
@@ -200,40 +154,21 @@ class TriangularSolver(LinearOperator):
         self._cast.clear()
 
     # -- solve ----------------------------------------------------------------
-    def _operands(self, tdt):
-        if tdt == self._values.dtype:
-            return self._values, self._diag
-        if tdt not in self._cast:
-            self._cast[tdt] = (self._values.to(tdt), self._diag.to(tdt))
-        return self._cast[tdt]
-
     def solve(self, b, out: Optional[DistArray] = None) -> DistArray:
         """x = T⁻¹ b for b of shape (n,) or (n, k).  out may alias b."""
-        b = asdistarray(b)
-        n = self.shape[0]
-        if b.ndim not in (1, 2) or b.shape[0] != n:
-            raise ValueError(
-                f"b has shape {b.shape}, expected ({n},) or ({n}, k)")
+        b = rowsched.as_rhs(b, self.shape[0], "b")
         tdt = common_value_dtype(self._values.dtype, b.local.dtype)
-        direct = (out is not None and out.local.dtype == tdt
-                  and out.shape == b.shape and out.local.is_contiguous())
-        x = out.local if direct else torch.empty(
-            b.local.shape, dtype=tdt, device=b.local.device)
+        x, direct = rowsched.result_buffer(b, out, tdt)
         if self._gpu:
             from . import kernels
 
-            vals, diag = self._operands(tdt)
+            vals, diag = rowsched.cast_operands(self._cast, self._values,
+                                                self._diag, tdt)
             kernels.trsv_solve(self, vals, diag,
                                b.local.to(tdt).contiguous(), x)
         else:
             x.copy_(self._solve_host(b.local, tdt))
-        if direct:
-            return out
-        res = DistArray.from_local(x, b.partition, b.shape)
-        if out is not None:
-            out.local.copy_(res.local.to(out.local.dtype))
-            return out
-        return res
+        return rowsched.finish_result(x, direct, b, out)
 
     def matvec(self, b, out=None):
         return self.solve(b, out=out)
@@ -269,8 +204,8 @@ def spsolve_triangular(A, b, lower=True, overwrite_A=False, overwrite_b=False,
     matrix and dropped when its values change.  overwrite_b solves in place
     when b is a DistArray of the result dtype; overwrite_A is accepted for
     scipy compatibility (A is never modified)."""
-    _single_rank("spsolve_triangular")
-    A = _as_csr(A)
+    single_rank("spsolve_triangular")
+    A = as_csr(A)
     key = ("trsv", bool(lower), bool(unit_diagonal))
     solver = A._plan_cache.get(key)
     if solver is None:
@@ -287,7 +222,7 @@ class _SGSOperator(LinearOperator):
     """z = (D+U)⁻¹ D (D+L)⁻¹ r, the inverse of M = (D+L) D⁻¹ (D+U)."""
 
     def __init__(self, A):
-        A = _as_csr(A)
+        A = as_csr(A)
         self._L = TriangularSolver(A, lower=True)
         self._U = TriangularSolver(A, lower=False)
         super().__init__(A.shape, dtype=A.dtype)
@@ -310,7 +245,7 @@ def sgs_preconditioner(A, ordering: str = "natural",
     preconditioner in the order of a greedy colouring of A (seed as in
     greedy_coloring), one launch per colour and direction — a
     gauss_seidel.MulticolorGaussSeidel."""
-    _single_rank("sgs_preconditioner")
+    single_rank("sgs_preconditioner")
     if ordering == "natural":
         return _SGSOperator(A)
     if ordering == "multicolor":

@@ -164,6 +164,19 @@ def test_poisson_greedy_and_red_black(poisson32):
     check_sweeps(rb, S, np.float64)
 
 
+def test_unused_colour_is_an_empty_segment():
+    """A caller's colouring that leaves colour 1 unused: the schedule has an
+    empty segment, skipped forwards and in reverse."""
+    from sparse import gallery
+    from sparse.linalg import MulticolorGaussSeidel
+
+    A = gallery.poisson2d(8, 8)
+    gs = MulticolorGaussSeidel(A, colors=2 * red_black(8, 8))
+    assert gs.ncolors == 3
+    assert gs.color_ptr.tolist() == [0, 32, 32, 64]
+    check_sweeps(gs, A.to_scipy_sparse_csr(), np.float64)
+
+
 @pytest.mark.parametrize("case", [dense_block, lower_bidiagonal])
 def test_sweeps_other_structures(case):
     from sparse.linalg import MulticolorGaussSeidel

@@ -1,4 +1,4 @@
-"""Colouring rounds (color.hip) and multicolour sweeps (mcgs.hip) vs the
+"""Colouring rounds (color.hip) and multicolour sweeps (relax.hip) vs the
 plain-Python / scipy oracles — all @gpu.
 
 Same oracles and inputs as test_mcgs.py (utils/mcgs_cases.py); the tests here
@@ -121,7 +121,7 @@ def test_sweeps_match_scipy_gpu(dt, idx):
     gs = MulticolorGaussSeidel(_device_csr(A, idx))
     assert np.array_equal(gs.colors.cpu().numpy(), py_greedy(A))
     # about 7 entries a row: 8 lanes per row in the populous colours
-    assert 8 in gs._sched[:, 2].tolist()
+    assert 8 in gs._sched[:, 3].tolist()
     _check_gpu(gs, A, dt)
 
 
@@ -134,8 +134,22 @@ def test_poisson_greedy_and_red_black_gpu(poisson32):
     _check_gpu(gs, S, np.float64)
     rb = MulticolorGaussSeidel(poisson32, colors=red_black(32, 32))
     assert rb.ncolors == 2 and rb.color_ptr.tolist() == [0, 512, 1024]
-    assert rb._sched[:, 2].tolist() == [8, 8]  # 4.9 entries a row
+    assert rb._sched[:, 3].tolist() == [8, 8]  # 4.9 entries a row
     _check_gpu(rb, S, np.float64)
+
+
+def test_unused_colour_is_an_empty_segment_gpu():
+    """A caller's colouring that leaves colour 1 unused: the schedule has an
+    empty segment, skipped (no launch) forwards and in reverse."""
+    from sparse import gallery
+    from sparse.linalg import MulticolorGaussSeidel
+
+    A = gallery.poisson2d(8, 8)
+    assert A._values.is_cuda
+    gs = MulticolorGaussSeidel(A, colors=2 * red_black(8, 8))
+    assert gs.ncolors == 3
+    assert gs.color_ptr.tolist() == [0, 32, 32, 64]
+    _check_gpu(gs, A.to_scipy_sparse_csr(), np.float64)
 
 
 @pytest.mark.parametrize("dt", types)
@@ -145,7 +159,7 @@ def test_long_rows_gpu(dt):
 
     A = dense_block(dt)
     gs = MulticolorGaussSeidel(_device_csr(A))
-    assert gs.ncolors >= 70 and 64 in gs._sched[:, 2].tolist()
+    assert gs.ncolors >= 70 and 64 in gs._sched[:, 3].tolist()
     _check_gpu(gs, A, dt, shapes=[(200,), (200, 3)])
 
 
@@ -155,7 +169,7 @@ def test_short_rows_gpu():
 
     A = lower_bidiagonal()
     gs = MulticolorGaussSeidel(_device_csr(A))
-    assert set(gs._sched[:, 2].tolist()) == {1}
+    assert set(gs._sched[:, 3].tolist()) == {1}
     _check_gpu(gs, A, np.float64)
 
 

@@ -1,4 +1,4 @@
-"""Level-scheduled triangular solve kernels (trsv.hip) vs scipy — all @gpu.
+"""Level-scheduled triangular solve kernels (relax.hip) vs scipy — all @gpu.
 
 Same oracle and inputs as test_trisolve.py (utils/trisolve_cases.py); the
 schedule-shape tests pin which kernel runs which levels and check the result.

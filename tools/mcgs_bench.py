@@ -72,7 +72,7 @@ def run_case(name, A, reps, emit, dry):
     emit(f"== {name}: n = {n}, nnz = {A.nnz}, colours = {gs.ncolors}, "
          f"rounds = {rounds}, class sizes "
          f"{' / '.join(f'{100.0 * s / max(n, 1):.1f}' for s in sizes)} %, "
-         f"lanes per row {sorted(set(gs._sched[:, 2].tolist()))}")
+         f"lanes per row {sorted(set(gs._sched[:, 3].tolist()))}")
     same = bool(torch.equal(colors.cpu(), host_colors(A)))
     emit(f"   colours equal to the sequential host op: {same}")
     assert same
