@@ -170,16 +170,11 @@ class ILU0(LinearOperator):
         if lc.values.dtype != self._fvals.dtype:
             raise ValueError(
                 f"refactor: dtype {A.dtype} differs from {self.dtype}")
-        for new, old in ((lc.indptr, self._indptr),
-                         (lc.indices, self._indices)):
-            same = (new.data_ptr() == old.data_ptr() and new.dtype == old.dtype
-                    and new.numel() == old.numel())
-            if not same and not (new.numel() == old.numel()
-                                 and new.device == old.device
-                                 and torch.equal(new.to(old.dtype), old)):
-                raise ValueError(
-                    "refactor: the matrix does not have the factorised "
-                    "structure (indptr / indices differ)")
+        if not (rowsched.same_structure(lc.indptr, self._indptr)
+                and rowsched.same_structure(lc.indices, self._indices)):
+            raise ValueError(
+                "refactor: the matrix does not have the factorised "
+                "structure (indptr / indices differ)")
         self._factor(lc.values)
         return self
 

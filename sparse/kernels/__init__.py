@@ -422,6 +422,26 @@ def ilu0_factor(fac, values, flag):
                       ls._order, ls._level_ptr, fac._sched, flag)
 
 
+# -- FSAI -------------------------------------------------------------------------
+def fsai_factor(fac, a_values, g_values, flag):
+    """Numeric FSAI into g_values (the pattern's layout) over the analysis of
+    an fsai.FSAI: one launch per non-empty length class on the current
+    stream, no host sync.  flag (one int64 word, preset >= n) receives the
+    smallest row index that broke down."""
+    from ..fsai import _WORK_VALUES
+
+    for lanes, rows, max_m in fac._classes:
+        nvals = 0
+        if lanes == 0:  # workspace slots, one per workgroup
+            slot = max_m * (max_m + 1) // 2 + max_m
+            nvals = slot * max(1, min(rows.numel(), _WORK_VALUES // slot))
+        work = torch.empty(nvals, dtype=g_values.dtype,
+                           device=g_values.device)
+        ext().fsai_factor(fac._a_indptr, fac._a_indices, a_values,
+                          fac._indptr, fac._indices, g_values, rows,
+                          int(lanes), int(max_m), work, flag)
+
+
 # -- multicolour Gauss-Seidel ---------------------------------------------------
 def color_round(indptr, indices, work_in, nwork: int, seed: int, colors,
                 work_out, count):

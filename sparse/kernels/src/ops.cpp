@@ -95,6 +95,9 @@ void trsv_solve_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                     at::Tensor, at::Tensor, at::Tensor, at::Tensor);
 void ilu0_factor_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
                      at::Tensor, at::Tensor, at::Tensor, at::Tensor);
+void fsai_factor_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor,
+                     at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
+                     at::Tensor, at::Tensor);
 void color_round_hip(at::Tensor, at::Tensor, at::Tensor, int64_t, int64_t,
                      at::Tensor, at::Tensor, at::Tensor);
 void mcgs_sweep_hip(at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor,
@@ -371,6 +374,9 @@ TORCH_LIBRARY(sparse_hip, m) {
   m.def("ilu0_factor(Tensor indptr, Tensor indices, Tensor(a!) values, "
         "Tensor diag_ptr, Tensor order, Tensor level_ptr, Tensor sched, "
         "Tensor(b!) flag) -> ()");
+  m.def("fsai_factor(Tensor a_indptr, Tensor a_indices, Tensor a_values, "
+        "Tensor p_indptr, Tensor p_indices, Tensor(a!) g_values, Tensor rows, "
+        "int lanes, int max_m, Tensor work, Tensor(b!) flag) -> ()");
   m.def("color_round(Tensor indptr, Tensor indices, Tensor work_in, "
         "int nwork, int seed, Tensor(a!) colors, Tensor(b!) work_out, "
         "Tensor(c!) count) -> ()");
@@ -419,6 +425,7 @@ TORCH_LIBRARY_IMPL(sparse_hip, CUDA, m) {
   m.impl("spgemm_compute", spgemm_compute_hip);
   m.impl("trsv_solve", trsv_solve_hip);
   m.impl("ilu0_factor", ilu0_factor_hip);
+  m.impl("fsai_factor", fsai_factor_hip);
   m.impl("color_round", color_round_hip);
   m.impl("mcgs_sweep", mcgs_sweep_hip);
 }

@@ -33,7 +33,7 @@ __all__ = [
     "bicg", "bicgstab", "gmres", "minres", "lsqr", "eigsh", "svds",
     "spsolve", "cg_axpby", "norm", "spsolve_triangular", "TriangularSolver",
     "sgs_preconditioner", "ilu0", "ILU0", "MulticolorGaussSeidel",
-    "greedy_coloring",
+    "greedy_coloring", "fsai", "FSAI",
 ]
 
 
@@ -1005,3 +1005,6 @@ from .ilu import ILU0, ilu0  # noqa: E402,F401
 # -- multicolour Gauss-Seidel (sparse/gauss_seidel.py) -------------------------
 from .gauss_seidel import (  # noqa: E402,F401
     MulticolorGaussSeidel, greedy_coloring)
+
+# -- factorised sparse approximate inverse (sparse/fsai.py) --------------------
+from .fsai import FSAI, fsai  # noqa: E402,F401

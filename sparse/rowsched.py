@@ -61,6 +61,16 @@ def row_index(indptr: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return counts, rows
 
 
+def same_structure(new: torch.Tensor, old: torch.Tensor) -> bool:
+    """Whether the index array `new` of a matrix handed to a refactor holds
+    what the analysed `old` one does: the same memory, or equal contents."""
+    if (new.data_ptr() == old.data_ptr() and new.dtype == old.dtype
+            and new.numel() == old.numel()):
+        return True
+    return (new.numel() == old.numel() and new.device == old.device
+            and torch.equal(new.to(old.dtype), old))
+
+
 def summed_diagonal(on: torch.Tensor, rows: torch.Tensor,
                     values: torch.Tensor, n: int,
                     first: Sequence[Tuple[torch.Tensor, Exception]] = ()
